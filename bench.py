@@ -9,8 +9,16 @@ R = 3 distinct resident batches (--rotate; step k reads batch k mod R, every bat
 so that no launch finds its bytes in the 256 MiB Infinity Cache; the line also
 carries the same box's pure-read probe rate (roofline.measured_peak: a reference, not a bound).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config A|B|C]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config A|B|C] [--full]
+                    [--dump-outputs DIR]
     torchrun --nproc-per-node N ... bench.py --gpus N     (one rank per GPU)
+
+A plain run sets up, warms up, times the K steps and prints the line. --full adds what takes
+runs of its own: every batch checked against the oracle / the reference (parity), the CPU
+baseline (cpu_baseline) and the ceiling probes (roofline.measured_peak and the fill / records
+/ slot ceilings); without it those fields are null or absent. --dump-outputs DIR writes what
+the last timed step returned as DIR/<name>.npy, for comparing two builds output for output
+(the inputs depend on the arguments alone).
 
 Multi-GPU: rank r owns a disjoint shard (packets [r*M, (r+1)*M) of one global batch,
 generated in place on its own GPU); there is NO data-path collective. A gloo process
@@ -111,6 +119,16 @@ def parse():
     p.add_argument("--steps", type=int, default=100)
     p.add_argument("--warmup", type=int, default=2000)
     p.add_argument("--config", default="A", choices=sorted(CONFIGS))
+    p.add_argument("--full", action="store_true",
+                   help="the device-resident line with everything beside its headline figure: "
+                        "parity of every batch against the oracle / the reference, the CPU "
+                        "baseline, and the read / fill / records / slot ceilings (probe runs of "
+                        "their own). Without it a run sets up, warms up, times the steps and "
+                        "prints the line (parity and cpu_baseline null, no ceilings)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step returned as "
+                        "DIR/<name>.npy (float32; outputs of more than a few MB as a fixed, "
+                        "seeded sample of their elements). Device-resident line only")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--cpu-reps", type=int, default=15,
                    help="timed single-thread passes of the CPU baseline sample")
@@ -310,6 +328,30 @@ def dma_to(arr, dev):
     out.copy_(h, non_blocking=True)
     torch.cuda.synchronize()
     return out
+
+
+DUMP_BUDGET_BYTES = 48 << 20  # all files of one --dump-outputs together (float32 elements)
+DUMP_SAMPLE_SEED = 20240607
+
+
+def dump_outputs(directory, arrays, suffix=""):
+    """--dump-outputs: each named output (a device tensor or numpy array of 8- or 16-bit
+    integers) as directory/<name><suffix>.npy in float32 (exact for those). The budget is
+    split evenly; an output over its share is written as a sample: its elements at sorted
+    indices drawn once from a fixed seed (the same indices for every run and build)."""
+    import torch
+    os.makedirs(directory, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // 4 // max(1, len(arrays))
+    for name, a in arrays.items():
+        flat = a.reshape(-1)
+        if flat.shape[0] > share:
+            idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).integers(
+                0, flat.shape[0], share, dtype=np.int64))
+            flat = flat[torch.from_numpy(idx).to(flat.device)] if torch.is_tensor(flat) \
+                else flat[idx]
+        if torch.is_tensor(flat):
+            flat = flat.cpu().numpy()
+        np.save(os.path.join(directory, name + suffix + ".npy"), flat.astype(np.float32))
 
 
 def make_chains(spec, dev):
@@ -634,6 +676,10 @@ CPU_REPS = 15
 def main():
     global CPU_REPS
     args = parse()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
+    if args.dump_outputs and (args.small or args.e2e):
+        raise SystemExit("--dump-outputs covers the device-resident line (not --small / --e2e)")
     CPU_REPS = max(1, args.cpu_reps)
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -670,6 +716,10 @@ def main():
         if layout not in ("strided", "csr", "rx", "tx", "rxslot", "csrslot", "txslot"):
             raise SystemExit("--e2e covers the configs A, B, C, RX, TX, RX2K, TX2K and C2K")
         return e2e(args, rank, world, local_rank, layout, n, plen)
+    if not args.full:
+        # a plain run: set-up, warm-up, the timed steps, the line. The checks, the CPU
+        # baseline and the ceiling probes are --full's
+        args.no_parity = args.no_cpu_baseline = args.no_ceiling = True
 
     # ---- this rank's shard, generated in place (global packets [rank*n, (rank+1)*n))
     spec = shard_spec(args.config, rank, world)
@@ -834,6 +884,26 @@ def main():
     if world > 1:
         dist.barrier()
 
+    if args.dump_outputs:
+        # what the last timed step (step k) returned, before anything below launches again
+        k = step_no[0] - 1
+        if layout in ("strided", "csr"):
+            last = {"checksums": outs[k % rot]}
+        elif layout in ("rx", "rxslot"):
+            last = {"verdicts": status}
+        elif layout == "txrec":  # 8-B records as their four 16-bit words (exact in float32)
+            last = {"record_words": records.cpu().numpy().view(np.uint16)}
+        elif layout == "csrslot":
+            last = {"checksums": out}
+        elif layout in ("tx", "txslot"):  # filled in place: the statuses and the frames
+            last = {"status": status, "frames": fbufs[k % len(fbufs)]}
+        else:  # chain; the fill form also wrote the header nodes
+            last = {"checksums": out}
+            if args.chain_fill:
+                cc = chain if k % rot == 0 else chain_rot[k % rot - 1]
+                last["headers"] = cc["buf"][:CHAIN_HDR_STRIDE * n]
+        dump_outputs(args.dump_outputs, last, suffix=f"_rank{rank}" if world > 1 else "")
+
     # Diagnostic, AFTER the timed region (not part of `value`): per-launch event pairs,
     # to expose outliers / clock ramps that the bracketed average smooths over.
     per_launch = []
@@ -872,7 +942,7 @@ def main():
     rot_parity = None
     cpu = None
     baseline = None  # rank 0's CPU baseline, run after every rank's check
-    if layout in FRAME_LAYOUTS and len(fbufs) > 1:
+    if layout in FRAME_LAYOUTS and len(fbufs) > 1 and args.full:
         # every copy processed at least once (the Tx fills write each in place); the last
         # step's outputs are checked below, and the copies must equal copy 0 afterwards
         while step_no[0] < len(fbufs) or (step_no[0] - 1) % len(fbufs) != 0:
@@ -931,7 +1001,7 @@ def main():
     else:
         # every rotation batch was read at least once (outside the timing if the run was
         # shorter than the rotation), and each is checked below
-        while step_no[0] < rot:
+        while args.full and step_no[0] < rot:
             step_w()
         torch.cuda.synchronize()
         host_out = out.cpu().numpy()
@@ -1001,7 +1071,7 @@ def main():
             slot_ceiling_fields["records_ceiling"] = rc
             slot_ceiling_fields["frac_of_records_ceiling"] = round(
                 rc["us"] / (avg_kernel_s * 1e6), 4)
-    if layout in ("rxslot", "csrslot", "txslot") and rank == 0:
+    if layout in ("rxslot", "csrslot", "txslot") and rank == 0 and args.full:
         ceil = slot_read_ceiling(args.config, spec)
         if ceil:
             kernel_gbps = payload / avg_kernel_s / 1e9
@@ -1043,13 +1113,14 @@ def main():
                              buf.numel() if layout in FRAME_LAYOUTS else
                              chain["buf"].numel() if layout == "chain" else total)),
                          "note": ("one batch, read by every step" if rot == 1 else
-                                  "step k reads copy k mod R of the batch (the same frames at "
-                                  "R addresses), every copy checked" if layout in FRAME_LAYOUTS
-                                  else "step k reads copy k mod R of the chains (the buffer "
-                                  "cloned, the chunk table rebased), every copy checked"
-                                  if layout == "chain"
-                                  else "step k reads batch k mod R (data seeds 42..42+R-1), "
-                                  "every batch checked")},
+                                  ("step k reads copy k mod R of the batch (the same frames at "
+                                   "R addresses)" if layout in FRAME_LAYOUTS
+                                   else "step k reads copy k mod R of the chains (the buffer "
+                                   "cloned, the chunk table rebased)" if layout == "chain"
+                                   else "step k reads batch k mod R (data seeds 42..42+R-1)")
+                                  + ("" if not args.full else
+                                     ", every batch checked" if layout in ("strided", "csr")
+                                     else ", every copy checked"))},
             **({"tx_fill": "split: read pass + scatter pass (both timed)" if args.tx_split else
                 "in-place, one pass"} if layout in ("tx", "txslot") else {}),
             **({"chain_fill": "checksum also stored big-endian into each header node"}

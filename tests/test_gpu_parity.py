@@ -585,7 +585,7 @@ def test_bench_two_ranks_one_gpu():
     env = dict(os.environ, AIPSTACK_BENCH_FORCE_DEVICE="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(port), "bench.py", "--gpus", "2",
-           "--steps", "5", "--warmup", "2", "--cpu-reps", "2"]
+           "--steps", "5", "--warmup", "2", "--cpu-reps", "2", "--full"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -1944,7 +1944,7 @@ def test_bench_torchrun_distinct_devices():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node",
            str(n_dev), "--master-addr", "127.0.0.1", "--master-port", str(port), "bench.py",
            "--gpus", str(n_dev), "--steps", "5", "--warmup", "2", "--cpu-reps", "1",
-           "--no-ceiling"]
+           "--no-ceiling", "--full"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.strip()][-1])
@@ -2053,7 +2053,7 @@ def test_bench_tx_fill_lines(config, split):
     every frame filled as the oracle fills it, the form named in the config."""
     import json
     r = subprocess.run([sys.executable, "bench.py", "--config", config, "--steps", "5",
-                        "--warmup", "5", "--no-cpu-baseline", "--no-ceiling"]
+                        "--warmup", "5", "--no-cpu-baseline", "--no-ceiling", "--full"]
                        + (["--tx-split"] if split else []), cwd=ROOT, capture_output=True,
                        text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -2062,6 +2062,34 @@ def test_bench_tx_fill_lines(config, split):
     if config == "TX2K":
         assert d["config"]["slot_stride"] == 2048
     assert d["config"]["tx_fill"].startswith("split" if split else "in-place")
+
+
+def test_bench_plain_run_dumps_last_step(oracle, tmp_path):
+    """A plain bench.py run (no --full) times exactly --steps launches and leaves the checks,
+    the CPU baseline and the ceiling probes out of its line; --dump-outputs writes what the
+    last timed step returned: step 4 of 2 + 3 read rotation batch 1 (data seed 43), whose
+    first 4096 checksums are compared with the oracle here."""
+    import json
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "2",
+                        "--dump-outputs", str(tmp_path / "out")], cwd=ROOT, capture_output=True,
+                       text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, r.stdout
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["value"] > 0
+    assert d["unit"] == "GiB/s" and d["higher_is_better"] is True and d["dtype"] == "u16"
+    # value is the batch's bytes over ms_per_step (one GPU)
+    assert d["value"] == pytest.approx((1 << 20) * 1500 / (d["ms_per_step"] / 1e3) / 2**30,
+                                       rel=1e-3)
+    assert d["parity"] is None and d["cpu_baseline"] is None
+    assert "measured_peak" not in d["roofline"]
+    assert os.listdir(tmp_path / "out") == ["checksums.npy"]
+    got = np.load(tmp_path / "out" / "checksums.npy")
+    assert got.dtype == np.float32 and got.shape == (1 << 20,)
+    host = np.empty(4096 * 1500, dtype=np.uint8)
+    synth.fill_host(host, synth.SEED_DATA + 1, 0)
+    assert np.array_equal(got[:4096], oracle.batch_strided(host, 1500, 1500, 4096))
 
 
 # ---- frame decisions pinned by the reference's own call sites (tests/golden/frame_ref.py) ---

@@ -15,6 +15,7 @@
 import ctypes
 import json
 import os
+import re
 import subprocess
 
 import numpy as np
@@ -70,8 +71,16 @@ def test_hook_library_needs_no_rocm():
     deps = _run(["ldd", HOOK_SO])
     libs = [ln.split()[0] for ln in deps.splitlines() if ln.strip()]
     assert not [l for l in libs if "hip" in l or "hsa" in l or "amd" in l or "rocm" in l], deps
+    # the hook's own closure: what the loader resolved by name, the vdso and the ELF
+    # interpreter. Any other absolute path is a library the environment preloads into every
+    # process (LD_PRELOAD, ld.so.preload): ldd lists it for any file, it is no dependency of
+    # the hook (whose DT_NEEDED entries are checked by name below)
+    own = [l for l in libs if not os.path.isabs(l) or l.startswith("/lib64/ld-linux")]
     assert all(l.startswith(("linux-vdso", "libc.so", "/lib64/ld-linux", "libstdc++", "libm.so",
-                             "libgcc_s")) for l in libs), deps
+                             "libgcc_s")) for l in own), deps
+    needed = re.findall(r"\(NEEDED\).*\[(.+)\]", _run(["readelf", "-d", HOOK_SO]))
+    assert needed and all(n.startswith(("libc.so", "libstdc++", "libm.so", "libgcc_s"))
+                          for n in needed), needed
     for lib in (HOOK_SO, HOOK_A):
         syms = _run(["nm", "-D" if lib.endswith(".so") else "-g", "--defined-only", lib])
         assert any(ln.split()[-1] == "IpChksumInverted" and " T " in ln

@@ -28,7 +28,7 @@ CONFIGS=${CONFIGS:-A B C A2K C2K RX RX2K TX TX2K TXREC CHAIN}
 if [ "$phase" = bench ] || [ "$phase" = all ]; then
   timeout -k 10 120 tools/build/hbm_peak > "$out/hbm_peak.jsonl"
   for c in $CONFIGS; do
-    timeout -k 10 300 python bench.py --config $c --per-launch \
+    timeout -k 10 300 python bench.py --config $c --per-launch --full \
         > "$out/bench_$c.json" 2> "$out/bench_$c.err"
   done
 fi
@@ -60,7 +60,7 @@ if [ "$phase" = rank8 ]; then
   for c in A C; do
     AIPSTACK_BENCH_FORCE_DEVICE=0 timeout -k 10 400 python -m torch.distributed.run --nnodes=1 \
         --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29531 bench.py --gpus 8 \
-        --config $c --steps 5 --warmup 2 --cpu-reps 3 > "$out/bench8_$c.json" 2> "$out/bench8_$c.err"
+        --config $c --steps 5 --warmup 2 --cpu-reps 3 --full > "$out/bench8_$c.json" 2> "$out/bench8_$c.err"
   done
 fi
 if [ "$phase" = small ]; then
