@@ -47,6 +47,11 @@ from .chksum import (  # noqa: E402
     tx_fill_records_slotted,
     tx_fill_slotted,
     apply_tx_records,
+    AIPSTACK_CHKSUM_MAX_SPLIT_HEADER,
+    AIPSTACK_TX_SPLIT_LAYOUT,
+    SplitFrames,
+    split_frames,
+    tx_fill_header_split,
 )
 
 LIB_PATH = _lib.LIB_PATH
@@ -61,4 +66,6 @@ __all__ = [
     "apply_tx_records", "contract_violations", "VIOLATION_CHUNK_LEN", "VIOLATION_PACKET_LEN",
     "VIOLATION_SPAN", "chksum_batch_slotted", "rx_verify_slotted", "slots_to_offsets",
     "tx_fill_records_slotted", "tx_fill_slotted", "ChksumEngineGroup",
+    "AIPSTACK_CHKSUM_MAX_SPLIT_HEADER", "AIPSTACK_TX_SPLIT_LAYOUT", "SplitFrames", "split_frames",
+    "tx_fill_header_split",
 ]

@@ -1131,6 +1131,160 @@ def _split_call(lib, name, frames, n, stream, workspace, args):
     workspace.record_stream(launch_stream)
 
 
+AIPSTACK_TX_SPLIT_LAYOUT = 9   # tx_fill_header_split: the split is out of layout, untouched
+AIPSTACK_CHKSUM_MAX_SPLIT_HEADER = 256
+
+
+def tx_fill_header_split(headers, hdr_stride: int, hdr_lens, chunk_addr, chunk_len, chunk_index,
+                         *, out=None, workspace=None, just_written: bool = False, stream=None):
+    """Tx fill of header-split segments on the GPU (``aipstack_chksum_tx_fill_hsplit``):
+    segment i = the first ``hdr_lens[i]`` bytes of slot i of ``headers`` (a device uint8 tensor
+    of n slots of ``hdr_stride`` bytes) followed by the chunks
+    ``[chunk_index[i], chunk_index[i+1])`` of the chunk table (as :func:`chksum_batch_chain`:
+    int64 device addresses, int32 lengths, int64 index of n+1 entries). Writes the IPv4 header
+    checksum and the TCP / UDP / ICMP checksum into the header slots, as :func:`tx_fill` does
+    to the linearised frames; the payload is only read. Returns one status per segment
+    (AIPSTACK_RX_* codes, or AIPSTACK_TX_SPLIT_LAYOUT for a segment whose split is out of
+    layout and was left untouched; chksum.h has the rule). ``workspace``: a device tensor of at
+    least ``aipstack_chksum_tx_fill_hsplit_workspace_bytes(n)`` bytes (else one is taken from
+    torch's allocator). ``just_written``: the AIPSTACK_CHKSUM_JUST_WRITTEN hint for the
+    payload read (results unchanged)."""
+    torch = _torch()
+    for t, name in ((headers, "headers"), (hdr_lens, "hdr_lens"), (chunk_addr, "chunk_addr"),
+                    (chunk_len, "chunk_len"), (chunk_index, "chunk_index")):
+        _require_device(t, name)
+        _same_device(headers, t, f"headers and {name}")
+    if chunk_addr.element_size() != 8 or chunk_len.element_size() != 4 \
+            or chunk_index.element_size() != 8:
+        raise ValueError("chunk_addr/chunk_index must be 64-bit, chunk_len 32-bit")
+    if hdr_lens.dtype not in (torch.int32, torch.uint32):
+        raise ValueError("hdr_lens must be an int32/uint32 device tensor")
+    n = chunk_index.numel() - 1
+    if n < 0:
+        raise ValueError("chunk_index must hold n+1 entries")
+    if hdr_lens.numel() < n:
+        raise ValueError("hdr_lens must hold n entries")
+    if hdr_stride <= 0 or n * hdr_stride > headers.numel() * headers.element_size():
+        raise ValueError("headers must hold n whole slots of hdr_stride bytes")
+    if chunk_addr.numel() != chunk_len.numel():
+        raise ValueError("chunk_addr and chunk_len must hold one entry per chunk")
+    out = _u8_out(out, n, headers)
+    if n == 0:
+        return out
+    if chunk_addr.numel() == 0:  # no chunk at all (pure ACKs): the C-ABI wants non-null tables
+        chunk_addr = torch.zeros(1, dtype=torch.int64, device=headers.device)
+        chunk_len = torch.zeros(1, dtype=torch.int32, device=headers.device)
+    lib = _lib.load()
+    need = int(lib.aipstack_chksum_tx_fill_hsplit_workspace_bytes(n))
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=headers.device)
+    else:
+        _require_device(workspace, "workspace")
+        _same_device(headers, workspace, "headers and workspace")
+    ws_bytes = workspace.numel() * workspace.element_size()
+    launch_stream = torch.cuda.current_stream(headers.device) if stream is None else stream
+    if not hasattr(launch_stream, "cuda_stream"):  # a raw hipStream_t handle
+        launch_stream = torch.cuda.ExternalStream(int(launch_stream), device=headers.device)
+    _check(lib.aipstack_chksum_tx_fill_hsplit(
+        headers.data_ptr(), hdr_stride, hdr_lens.data_ptr(), chunk_addr.data_ptr(),
+        chunk_len.data_ptr(), chunk_index.data_ptr(), n, out.data_ptr(), workspace.data_ptr(),
+        ws_bytes, AIPSTACK_CHKSUM_JUST_WRITTEN if just_written else 0,
+        _stream_handle(launch_stream)), "aipstack_chksum_tx_fill_hsplit")
+    # as _split_call: the allocator must not reuse the workspace (or a stand-in chunk table)
+    # before the launch stream has passed the call
+    for t in (workspace, chunk_addr, chunk_len):
+        t.record_stream(launch_stream)
+    return out
+
+
+class SplitFrames:
+    """What :func:`split_frames` returns (host arrays): ``headers`` (n slots of ``hdr_stride``
+    bytes), ``hdr_lens`` (uint32), ``payload`` (uint8, every chunk's bytes) and ``chunks``
+    (per segment, its ``(offset into payload, length)`` chunks in order)."""
+
+    def __init__(self, headers, hdr_stride, hdr_lens, payload, chunks):
+        self.headers, self.hdr_stride, self.hdr_lens = headers, hdr_stride, hdr_lens
+        self.payload, self.chunks = payload, chunks
+
+    def __iter__(self):  # headers, hdr_lens, payload, chunks = split_frames(...)
+        return iter((self.headers, self.hdr_lens, self.payload, self.chunks))
+
+    def chunk_table(self, payload_base: int = 0):
+        """(addr uint64, len uint32, index uint64) of the chunk table with the payload buffer
+        at address ``payload_base`` (a device copy's ``data_ptr()``)."""
+        addr = [payload_base + o for seg in self.chunks for o, _ in seg]
+        lens = [l for seg in self.chunks for _, l in seg]
+        index = np.zeros(len(self.chunks) + 1, dtype=np.uint64)
+        index[1:] = np.cumsum([len(seg) for seg in self.chunks])
+        return np.array(addr, dtype=np.uint64), np.array(lens, dtype=np.uint32), index
+
+    def linearise(self, headers=None, payload=None):
+        """The segments back to back again: (uint8 buffer, uint64 offsets of n+1 entries), from
+        this layout's arrays or from ``headers`` / ``payload`` given in their place."""
+        h = self.headers if headers is None else np.asarray(headers).reshape(-1).view(np.uint8)
+        p = self.payload if payload is None else np.asarray(payload).reshape(-1).view(np.uint8)
+        parts, offs = [], [0]
+        for i, seg in enumerate(self.chunks):
+            s = i * self.hdr_stride
+            parts.append(h[s:s + int(self.hdr_lens[i])])
+            parts += [p[o:o + l] for o, l in seg]
+            offs.append(offs[-1] + int(self.hdr_lens[i]) + sum(l for _, l in seg))
+        buf = np.concatenate(parts) if parts else np.zeros(0, dtype=np.uint8)
+        return buf.astype(np.uint8, copy=False), np.array(offs, dtype=np.uint64)
+
+
+def split_frames(frames, offsets, split_at, *, hdr_stride: int, payload_pieces=None,
+                 payload_gap: int = 0, reverse: bool = False) -> SplitFrames:
+    """Host helper: lay linear frames out as header-split segments. Frame i =
+    ``frames[offsets[i]:offsets[i+1]]``; its first ``split_at[i]`` bytes (clipped to the frame
+    and to ``hdr_stride``) go into header slot i, the rest into a payload buffer, cut into the
+    chunk lengths ``payload_pieces[i]`` (a sequence; the last chunk takes what remains, empty
+    chunks are dropped; None = one chunk). ``payload_gap`` bytes separate consecutive chunks in
+    the payload buffer (so chunks land at odd addresses); ``reverse`` places them in reverse
+    memory order. Slot bytes past a header are 0xEE, gaps 0xDD."""
+    fr = np.asarray(frames).reshape(-1).view(np.uint8)
+    off = np.asarray(offsets, dtype=np.uint64).astype(np.int64)
+    n = off.size - 1
+    if hdr_stride <= 0:
+        raise ValueError("hdr_stride must be positive")
+    headers = np.full(max(n, 0) * hdr_stride, 0xEE, dtype=np.uint8)
+    hdr_lens = np.zeros(max(n, 0), dtype=np.uint32)
+    pieces = []  # (segment, bytes)
+    per_seg = []
+    for i in range(n):
+        f = fr[off[i]:off[i + 1]]
+        h = max(0, min(int(split_at[i]), f.size, hdr_stride))
+        hdr_lens[i] = h
+        headers[i * hdr_stride:i * hdr_stride + h] = f[:h]
+        rest = f[h:]
+        cuts = list(payload_pieces[i]) if payload_pieces is not None else []
+        segs, at = [], 0
+        for c in cuts:
+            c = min(int(c), rest.size - at)
+            if c > 0:
+                segs.append(rest[at:at + c])
+                at += c
+        if at < rest.size:
+            segs.append(rest[at:])
+        per_seg.append(len(segs))
+        pieces += segs
+    # place the chunks: in order or reversed, payload_gap bytes apart
+    order = range(len(pieces) - 1, -1, -1) if reverse else range(len(pieces))
+    where = [0] * len(pieces)
+    at = payload_gap
+    for k in order:
+        where[k] = at
+        at += pieces[k].size + payload_gap
+    payload = np.full(max(at, 1), 0xDD, dtype=np.uint8)
+    for k, pc in enumerate(pieces):
+        payload[where[k]:where[k] + pc.size] = pc
+    chunks, k = [], 0
+    for cnt in per_seg:
+        chunks.append([(where[k + j], int(pieces[k + j].size)) for j in range(cnt)])
+        k += cnt
+    return SplitFrames(headers, hdr_stride, hdr_lens, payload, chunks)
+
+
 def tx_fill_records(frames, offsets, *, out=None, stream=None):
     """The split Tx fill's read pass alone (``aipstack_chksum_tx_fill_records``): one 8-byte
     record per frame, nothing written into the frames. Record i = ``w0 | w1 << 32`` with

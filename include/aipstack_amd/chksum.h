@@ -216,6 +216,51 @@ int aipstack_chksum_tx_fill_records_slotted(const void *d_base, uint64_t slot_st
                                             const uint32_t *d_len, uint64_t n,
                                             uint64_t *d_records, void *stream);
 
+/* ---- header-split Tx fill: a header ring + send-ring chunks -------------------------- */
+
+/* Status of aipstack_chksum_tx_fill_hsplit: the segment's split does not satisfy the layout
+ * rule below; nothing of it was written. The caller linearises such a segment and uses
+ * aipstack_chksum_tx_fill. */
+#define AIPSTACK_TX_SPLIT_LAYOUT 9
+/* Largest d_hdr_len of the header-split fill. */
+#define AIPSTACK_CHKSUM_MAX_SPLIT_HEADER 256u
+
+/* Tx fill of segments as the reference's send side builds them: a header node in its own
+ * buffer followed by chunks of the send ring (tcp/IpTcpProto_output.h:1251-1277,
+ * udp/IpUdpProto.h:164-179, ip/IpStack.h:632-663), filled where they lie. Segment i is one
+ * Ethernet frame in two parts: its first d_hdr_len[i] bytes at d_hdr + i*hdr_stride, the rest
+ * the chunks [d_chunk_index[i], d_chunk_index[i+1]) of the chunk table, in order (form and
+ * contract of aipstack_chksum_batch_chain: any alignment, each chunk <= 65535 bytes, n+1 index
+ * entries; 0 chunks = e.g. a pure ACK). With L = d_hdr_len[i] + its chunk bytes, the result is
+ * what aipstack_chksum_tx_fill does to the L-byte linearised frame: the same d_status[i], the
+ * same IPv4 header checksum and TCP / UDP (0 -> 0xFFFF) / ICMP checksum stored big-endian into
+ * the header slot (fragments, other protocols and L4-malformed segments: the IPv4 field only;
+ * _NOT_IP4 and _DROP_IP_MALFORMED: untouched). Both fields are taken as 0 whatever they hold,
+ * so a call can be repeated (or replayed from a graph). Payload chunks are never written.
+ *
+ * Layout rule (else d_status[i] = AIPSTACK_TX_SPLIT_LAYOUT, segment untouched):
+ * d_hdr_len[i] <= min(hdr_stride, AIPSTACK_CHKSUM_MAX_SPLIT_HEADER); every byte the linear
+ * fill would parse or write lies in the header slot, stage by stage -- the Ethernet header
+ * (14 bytes), the 20-byte IPv4 minimum, the IPv4 header with options (14 + 4*IHL), the fixed
+ * L4 header (TCP 20, UDP 8, ICMP 8): a frame that has a stage's bytes (by L) while
+ * d_hdr_len[i] does not cover them is out of layout; and for a non-fragment TCP / UDP / ICMP
+ * segment the bytes the L4 checksum covers (total length - header length, or the UDP length)
+ * end exactly at L (no trailing padding).
+ *
+ * Three stream-ordered passes: a header pass (parse, IPv4 checksum, the L4 sum's seed), the
+ * chained batch over the chunk table, a finish pass that stores the fields and d_status.
+ * d_workspace: caller-owned, 8-byte aligned, at least
+ * aipstack_chksum_tx_fill_hsplit_workspace_bytes(n) (<= 16*n + 256) bytes, free again once the
+ * stream passes the call. flags: AIPSTACK_CHKSUM_JUST_WRITTEN (the payload read); other bits
+ * are ignored. _EINVAL before any work for a null pointer, hdr_stride == 0, n > 2^40, a short
+ * or misaligned workspace; n == 0 is a no-op. Oversized chunks: _CHUNK_LEN (diagnostics). */
+uint64_t aipstack_chksum_tx_fill_hsplit_workspace_bytes(uint64_t n);
+int aipstack_chksum_tx_fill_hsplit(void *d_hdr, uint64_t hdr_stride, const uint32_t *d_hdr_len,
+                                   const uint64_t *d_chunk_addr, const uint32_t *d_chunk_len,
+                                   const uint64_t *d_chunk_index, uint64_t n,
+                                   uint8_t *d_status, void *d_workspace,
+                                   uint64_t workspace_bytes, uint32_t flags, void *stream);
+
 /* ---- 3. host-memory streaming engine ----------------------------------------------- */
 
 /* The reference's packet path starts and ends in host memory (TAP read()/write(),
