@@ -52,6 +52,13 @@ from .chksum import (  # noqa: E402
     SplitFrames,
     split_frames,
     tx_fill_header_split,
+    AIPSTACK_TCP_BURST_FIN,
+    AIPSTACK_TCP_SEGMENT_HEADER,
+    AIPSTACK_TX_BURST_INVALID,
+    TCP_BURST_DTYPE,
+    TcpSegments,
+    tcp_burst_layout,
+    tcp_tx_segment,
 )
 
 LIB_PATH = _lib.LIB_PATH
@@ -68,4 +75,6 @@ __all__ = [
     "tx_fill_records_slotted", "tx_fill_slotted", "ChksumEngineGroup",
     "AIPSTACK_CHKSUM_MAX_SPLIT_HEADER", "AIPSTACK_TX_SPLIT_LAYOUT", "SplitFrames", "split_frames",
     "tx_fill_header_split",
+    "AIPSTACK_TCP_BURST_FIN", "AIPSTACK_TCP_SEGMENT_HEADER", "AIPSTACK_TX_BURST_INVALID",
+    "TCP_BURST_DTYPE", "TcpSegments", "tcp_burst_layout", "tcp_tx_segment",
 ]

@@ -1197,6 +1197,183 @@ def tx_fill_header_split(headers, hdr_stride: int, hdr_lens, chunk_addr, chunk_l
     return out
 
 
+AIPSTACK_TCP_SEGMENT_HEADER = 54   # Ethernet 14 + IPv4 20 + TCP 20
+AIPSTACK_TCP_BURST_FIN = 1         # burst flag: the last segment carries FIN|PSH
+AIPSTACK_TX_BURST_INVALID = 10     # tcp_tx_segment: the segment's burst breaks the contract
+
+# ``aipstack_tcp_burst`` (chksum.h): one TCP data burst of one connection, host-made.
+TCP_BURST_DTYPE = np.dtype({
+    "names": ["data_addr", "data_len", "seq", "psh_offset", "mss", "ip_id", "flags", "reserved",
+              "hdr"],
+    "formats": [("<u8", (2,)), ("<u4", (2,)), "<u4", "<u4", "<u2", "<u2", "u1", ("u1", (3,)),
+                ("u1", (56,))],
+    "offsets": [0, 16, 24, 28, 32, 34, 36, 37, 40],
+    "itemsize": 96,
+})
+assert TCP_BURST_DTYPE.itemsize == 96
+
+
+def tcp_burst_layout(bursts):
+    """Host side of :func:`tcp_tx_segment` (``aipstack_tcp_burst_layout``, no GPU): the segment
+    and chunk counts of each burst of ``bursts`` (a ``TCP_BURST_DTYPE`` array) as running sums,
+    ``(seg_index, chunk_base)``, uint64 arrays of ``len(bursts) + 1`` entries. Raises
+    :class:`ChksumError` (``AIPSTACK_CHKSUM_EINVAL``) if a burst breaks the contract."""
+    b = np.ascontiguousarray(bursts, dtype=TCP_BURST_DTYPE).reshape(-1)
+    seg_index = np.zeros(b.size + 1, dtype=np.uint64)
+    chunk_base = np.zeros(b.size + 1, dtype=np.uint64)
+    _check(_lib.load().aipstack_tcp_burst_layout(b.ctypes.data if b.size else None, b.size,
+                                                 seg_index.ctypes.data, chunk_base.ctypes.data),
+           "aipstack_tcp_burst_layout")
+    return seg_index, chunk_base
+
+
+def _launch_stream(stream, dev):
+    torch = _torch()
+    launch_stream = torch.cuda.current_stream(dev) if stream is None else stream
+    if not hasattr(launch_stream, "cuda_stream"):  # a raw hipStream_t handle
+        launch_stream = torch.cuda.ExternalStream(int(launch_stream), device=dev)
+    return launch_stream
+
+
+class TcpSegments:
+    """What :func:`tcp_tx_segment` leaves (device tensors): ``headers`` (uint8, n slots of
+    ``hdr_stride`` bytes), the chunk table ``chunk_addr`` (int64) / ``chunk_len`` (int32) /
+    ``chunk_index`` (int64, n + 1 entries) and ``status`` (uint8, n). ``hdr_lens`` (int32, all
+    54, made on first use) completes the arguments of :func:`tx_fill_header_split`; the chunk
+    table is what :func:`chksum_batch_chain` takes."""
+
+    def __init__(self, headers, hdr_stride, chunk_addr, chunk_len, chunk_index, status):
+        self.headers, self.hdr_stride = headers, hdr_stride
+        self.chunk_addr, self.chunk_len, self.chunk_index = chunk_addr, chunk_len, chunk_index
+        self.status = status
+        self._hdr_lens = None
+
+    @property
+    def n_segments(self) -> int:
+        return self.chunk_index.numel() - 1
+
+    @property
+    def hdr_lens(self):
+        if self._hdr_lens is None:
+            torch = _torch()
+            self._hdr_lens = torch.full((self.n_segments,), AIPSTACK_TCP_SEGMENT_HEADER,
+                                        dtype=torch.int32, device=self.headers.device)
+        return self._hdr_lens
+
+
+def tcp_tx_segment(bursts, seg_index, chunk_base, *, hdr_stride: int = 64, headers=None,
+                   just_written: bool = False, stream=None, workspace=None, out=None,
+                   n_segments: Optional[int] = None, n_chunks: Optional[int] = None,
+                   device=None) -> TcpSegments:
+    """TCP burst segmentation on the GPU (``aipstack_tcp_tx_segment``): for every burst of
+    ``bursts`` (``TCP_BURST_DTYPE``), every segment's complete 54-byte frame header in slot i of
+    a header ring, the chunk table of its data bytes and both checksums -- what the reference's
+    ``pcb_output_segment`` / ``sendSegment`` / ``sendIp4DgramFast`` loop produces.
+
+    ``bursts``, ``seg_index``, ``chunk_base``: host numpy arrays (the latter two from
+    :func:`tcp_burst_layout`; uploaded here), or device tensors already resident (uint8 /
+    int64 / int64), in which case ``n_segments`` and ``n_chunks`` (the last index entries) must
+    be given. ``headers``: the ring to write (device uint8 tensor of at least n slots of
+    ``hdr_stride`` bytes; else a fresh one). ``out``: a :class:`TcpSegments` whose tensors are
+    reused (``headers`` / ``hdr_stride`` then come from it). ``workspace``: a device tensor of
+    at least ``aipstack_tcp_tx_segment_workspace_bytes(n)`` bytes, 8-byte aligned.
+    ``just_written``: the AIPSTACK_CHKSUM_JUST_WRITTEN hint for the data read. Status per
+    segment: ``AIPSTACK_RX_ACCEPT``, or ``AIPSTACK_TX_BURST_INVALID`` (slot untouched)."""
+    torch = _torch()
+    if hasattr(seg_index, "data_ptr"):
+        if n_segments is None or n_chunks is None:
+            raise ValueError("device seg_index/chunk_base need n_segments and n_chunks")
+        for t, name in ((bursts, "bursts"), (seg_index, "seg_index"), (chunk_base, "chunk_base")):
+            _require_device(t, name)
+        if seg_index.element_size() != 8 or chunk_base.element_size() != 8:
+            raise ValueError("seg_index/chunk_base must be 64-bit")
+        if seg_index.numel() != chunk_base.numel() or seg_index.numel() < 1:
+            raise ValueError("seg_index and chunk_base must hold n_bursts + 1 entries each")
+        n_bursts = seg_index.numel() - 1
+        if bursts.numel() * bursts.element_size() < 96 * n_bursts:
+            raise ValueError("bursts must hold n_bursts descriptors of 96 bytes")
+        d_bursts, d_seg, d_base = bursts, seg_index, chunk_base
+        dev = bursts.device
+    else:
+        b = np.ascontiguousarray(bursts, dtype=TCP_BURST_DTYPE).reshape(-1)
+        si = np.array(seg_index, dtype=np.uint64).reshape(-1)    # (copies: torch wants them writable)
+        cb = np.array(chunk_base, dtype=np.uint64).reshape(-1)
+        if si.size != b.size + 1 or cb.size != b.size + 1:
+            raise ValueError("seg_index and chunk_base must hold len(bursts) + 1 entries each")
+        n_bursts = b.size
+        n_segments = int(si[-1]) if n_segments is None else n_segments
+        n_chunks = int(cb[-1]) if n_chunks is None else n_chunks
+        if out is not None:
+            dev = out.headers.device
+        elif headers is not None:
+            dev = headers.device
+        else:
+            dev = torch.device("cuda" if device is None else device)
+        raw = np.zeros(max(b.size, 1) * 96, dtype=np.uint8)
+        raw[:b.size * 96] = b.view(np.uint8)
+        with torch.cuda.stream(_launch_stream(stream, dev)):  # uploads ordered before the call
+            d_bursts = torch.from_numpy(raw).to(dev)
+            d_seg = torch.from_numpy(si.view(np.int64)).to(dev)
+            d_base = torch.from_numpy(cb.view(np.int64)).to(dev)
+    n, nc = int(n_segments), int(n_chunks)
+    if n < 0 or nc < 0:
+        raise ValueError("n_segments and n_chunks must not be negative")
+    if out is not None:
+        headers, hdr_stride = out.headers, out.hdr_stride
+        for t, name, cnt, size in ((out.chunk_addr, "chunk_addr", nc, 8),
+                                   (out.chunk_len, "chunk_len", nc, 4),
+                                   (out.chunk_index, "chunk_index", n + 1, 8),
+                                   (out.status, "status", n, 1)):
+            _require_device(t, f"out.{name}")
+            if t.element_size() != size or t.numel() < cnt:
+                raise ValueError(f"out.{name} is too small or of the wrong element size")
+        if out.chunk_index.numel() != n + 1 or out.status.numel() != n:
+            raise ValueError("out.chunk_index / out.status must hold n + 1 / n entries")
+        res = out
+    if hdr_stride < AIPSTACK_TCP_SEGMENT_HEADER:
+        raise ValueError("hdr_stride must be at least 54")
+    if headers is None:
+        headers = torch.zeros(max(n * hdr_stride, 1), dtype=torch.uint8, device=dev)
+    else:
+        _require_device(headers, "headers")
+        if headers.element_size() != 1 or headers.numel() < n * hdr_stride:
+            raise ValueError("headers must be a uint8 tensor of n whole slots of hdr_stride bytes")
+    _same_device(headers, d_bursts, "headers and bursts")
+    if out is None:
+        res = TcpSegments(headers, hdr_stride,
+                          torch.zeros(max(nc, 1), dtype=torch.int64, device=dev)[:nc],
+                          torch.zeros(max(nc, 1), dtype=torch.int32, device=dev)[:nc],
+                          torch.zeros(n + 1, dtype=torch.int64, device=dev),
+                          torch.empty(n, dtype=torch.uint8, device=dev))
+    if n == 0:
+        return res
+    lib = _lib.load()
+    need = int(lib.aipstack_tcp_tx_segment_workspace_bytes(n))
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    else:
+        _require_device(workspace, "workspace")
+        _same_device(headers, workspace, "headers and workspace")
+    ws_bytes = workspace.numel() * workspace.element_size()
+    launch_stream = _launch_stream(stream, dev)
+    # no chunk at all (FIN-only bursts): the C-ABI wants non-null tables (storage of 1 entry)
+    ca, cl = res.chunk_addr, res.chunk_len
+    if nc == 0 and (ca.data_ptr() == 0 or cl.data_ptr() == 0):
+        ca = torch.zeros(1, dtype=torch.int64, device=dev)
+        cl = torch.zeros(1, dtype=torch.int32, device=dev)
+    _check(lib.aipstack_tcp_tx_segment(
+        d_bursts.data_ptr(), d_seg.data_ptr(), d_base.data_ptr(), n_bursts, n, nc,
+        headers.data_ptr(), hdr_stride, ca.data_ptr(), cl.data_ptr(), res.chunk_index.data_ptr(),
+        res.status.data_ptr(), workspace.data_ptr(), ws_bytes,
+        AIPSTACK_CHKSUM_JUST_WRITTEN if just_written else 0, _stream_handle(launch_stream)),
+        "aipstack_tcp_tx_segment")
+    # the allocator must not reuse the workspace or the uploaded descriptors before the launch
+    # stream has passed the call
+    for t in (workspace, d_bursts, d_seg, d_base, ca, cl):
+        t.record_stream(launch_stream)
+    return res
+
+
 class SplitFrames:
     """What :func:`split_frames` returns (host arrays): ``headers`` (n slots of ``hdr_stride``
     bytes), ``hdr_lens`` (uint32), ``payload`` (uint8, every chunk's bytes) and ``chunks``

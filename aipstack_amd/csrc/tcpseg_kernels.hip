@@ -1,0 +1,390 @@
+// aipstack_amd -- TCP burst segmentation: the reference's send loop for a burst of one
+// connection's data (pcb_output_active -> pcb_output_segment -> PcbOutputHelper::sendSegment ->
+// IpStack::sendIp4DgramFast; tcp/IpTcpProto_output.h:1056-1120, 1218-1335, ip/IpStack.h:564-663)
+// for a batch of bursts. The host uploads one 96-byte descriptor per burst (aipstack_tcp_burst:
+// the header template prepareCommon / prepareSendIp4Dgram leave, and what changes per segment
+// as arithmetic); the GPU emits every segment's 54-byte header, the chunk table of its data and
+// both checksums. Three stream-ordered launches:
+//   1. tcpseg_plan_kernel, one segment per lane: the burst that owns the segment (upper bound
+//      in the running segment counts, minus one: bursts of no segment are stepped over), the
+//      burst's contract, the segment's chunk entries and index entry, the seed of the L4 sum
+//      (pseudo-header, the template's TCP words, seq, offset/flags, tcp_len) and the IPv4 header
+//      checksum, both as arithmetic on header words. Seeds (dense uint32) and one 8-byte record
+//      per segment (owner burst, IPv4 checksum, valid) go to the workspace.
+//   2. the chained batch (aipstack_chksum_batch_chain), unchanged, over the table just written
+//      with the seeds as its states: seed (+) data, 16 bits per segment. The 20 TCP header bytes
+//      are an even count, so the data always starts at an even logical position: no swapped
+//      seed (hsplit_kernels.hip has the odd case).
+//   3. tcpseg_emit_kernel, one segment per lane: the 54 bytes from the template and the
+//      per-segment words, both checksums inserted, the slot stored whole. Slots are never
+//      loaded. A 64-byte ring on a 64-byte boundary is stored in whole lines: the wave passes
+//      its 64 slots through LDS so that each of its four 16-byte store instructions covers
+//      1 KiB of contiguous memory. Any other stride or alignment: per-lane unaligned stores.
+//
+// Header words are summed as the repository does everywhere: little-endian 16-bit halves of the
+// template's dwords (every field lies at an even offset of the 8-byte aligned template), folded
+// and byte-swapped once, then the per-segment big-endian words added.
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "aipstack_amd/chksum.h"
+#include "chksum_internal.h"
+#include "tcpseg_common.h"
+
+namespace aipstack_amd {
+namespace {
+
+constexpr int kTsBlock = 256;
+constexpr int kTsWave = 64;
+
+// The record of segment i (workspace, 8 bytes): bits 0-39 the burst that owns it, 40-55 the
+// IPv4 header checksum, 56 = valid (emit the slot; else status AIPSTACK_TX_BURST_INVALID).
+constexpr uint64_t kRecBurstMask = (1ull << 40) - 1u;
+constexpr uint64_t kRecValid = 1ull << 56;
+
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+#define AIPSTACK_TS_GLOBAL __attribute__((address_space(1)))
+typedef AIPSTACK_TS_GLOBAL u32x4 g_line;
+typedef AIPSTACK_TS_GLOBAL u32x4 g_quad_any __attribute__((aligned(1)));
+typedef AIPSTACK_TS_GLOBAL uint32_t g_u32_any __attribute__((aligned(1)));
+typedef AIPSTACK_TS_GLOBAL uint16_t g_u16_any __attribute__((aligned(1)));
+typedef AIPSTACK_TS_GLOBAL uint8_t g_u8;
+
+__device__ __forceinline__ uint32_t ts_bswap16(uint32_t x) {
+    return ((x & 0xFFu) << 8) | ((x >> 8) & 0xFFu);
+}
+
+// x mod 0xFFFF with a nonzero multiple as 0xFFFF: zero only for x = 0.
+__device__ __forceinline__ uint32_t ts_fold16(uint32_t x) {
+    x = (x & 0xFFFFu) + (x >> 16);
+    return (x & 0xFFFFu) + (x >> 16);
+}
+
+__device__ __forceinline__ uint64_t ts_uniform64(uint64_t v) {
+    return ((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(v >> 32)) << 32) |
+           __builtin_amdgcn_readfirstlane((uint32_t)v);
+}
+
+// The first j in [lo, hi] with idx[j] > i (hi if there is none); reads entries in [lo, hi).
+__device__ __forceinline__ uint64_t ts_upper_bound(const uint64_t *__restrict__ idx, uint64_t lo,
+                                                   uint64_t hi, uint64_t i) {
+    while (lo < hi) {
+        const uint64_t mid = lo + ((hi - lo) >> 1);
+        if (idx[mid] <= i) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// The template's 14 dwords (56 bytes; the struct is 8-byte aligned and hdr lies at offset 40).
+struct Template {
+    uint32_t t[14];
+};
+
+__device__ __forceinline__ Template ts_template(const aipstack_tcp_burst *__restrict__ d) {
+    Template r;
+    const uint2 *p = reinterpret_cast<const uint2 *>(d->hdr);
+#pragma unroll
+    for (int q = 0; q < 7; ++q) {
+        const uint2 v = p[q];
+        r.t[2 * q] = v.x;
+        r.t[2 * q + 1] = v.y;
+    }
+    return r;
+}
+
+// What changes per segment (tcp/IpTcpProto_output.h:1069-1102, ip/IpStack.h:640-653).
+struct SegWords {
+    uint64_t start;
+    uint32_t len, seq, offset_flags, total_len, ident;
+};
+
+__device__ __forceinline__ SegWords ts_segment(const aipstack_tcp_burst *__restrict__ d,
+                                               const TcpBurstShape &s, uint64_t k) {
+    SegWords w;
+    const uint64_t mss = d->mss;
+    w.start = k * mss;  // k < S <= 2^32, mss < 2^16
+    const uint64_t rest = s.D - w.start;
+    w.len = (uint32_t)(rest < mss ? rest : mss);
+    w.seq = d->seq + (uint32_t)w.start;
+    uint32_t fl = 0x5010u;  // Tcp4EncodeOffset(5) | Ack
+    const uint64_t psh = d->psh_offset;
+    if (psh > w.start && psh <= w.start + w.len) fl |= 0x08u;                       // Psh
+    if ((d->flags & AIPSTACK_TCP_BURST_FIN) != 0u && k + 1 == s.S) fl |= 0x09u;  // Fin|Psh
+    w.offset_flags = fl;
+    w.total_len = 40u + w.len;
+    w.ident = ((uint32_t)d->ip_id + (uint32_t)k) & 0xFFFFu;
+    return w;
+}
+
+// Little-endian halves of the source and destination address (frame bytes 26-33).
+__device__ __forceinline__ uint32_t ts_addr_halves(const Template &h) {
+    return (h.t[6] >> 16) + (h.t[7] & 0xFFFFu) + (h.t[7] >> 16) + (h.t[8] & 0xFFFFu);
+}
+
+// The IPv4 header checksum: version/IHL/DSCP, flags/fragment offset, TTL/protocol and the
+// addresses from the template, total length and ident per segment, the field as 0.
+__device__ __forceinline__ uint32_t ts_ip_checksum(const Template &h, const SegWords &w) {
+    const uint32_t le = (h.t[3] >> 16) + (h.t[5] & 0xFFFFu) + (h.t[5] >> 16) + ts_addr_halves(h);
+    const uint32_t be = ts_bswap16(ts_fold16(le)) + w.total_len + w.ident;
+    return ~ts_fold16(be) & 0xFFFFu;
+}
+
+// The State the data chain is resumed from: the pseudo-header (addresses, protocol 6, tcp_len)
+// and the 20 TCP header bytes (ports, ack, window, urgent pointer from the template; seq and
+// offset/flags per segment; the checksum field as 0). At most 13 words: far below 2^32.
+__device__ __forceinline__ uint32_t ts_l4_seed(const Template &h, const SegWords &w) {
+    const uint32_t le = ts_addr_halves(h) + (h.t[8] >> 16) + (h.t[9] & 0xFFFFu) + (h.t[10] >> 16) +
+                        (h.t[11] & 0xFFFFu) + (h.t[12] & 0xFFFFu) + (h.t[13] & 0xFFFFu);
+    return ts_bswap16(ts_fold16(le)) + 6u + (20u + w.len) + (w.seq >> 16) + (w.seq & 0xFFFFu) +
+           w.offset_flags;
+}
+
+// A burst's view of the caller's index: segments [sb, se), chunks [cb, ce).
+struct BurstRange {
+    uint64_t sb, se, cb, ce;
+};
+
+__device__ __forceinline__ BurstRange ts_range(const uint64_t *__restrict__ seg_index,
+                                               const uint64_t *__restrict__ chunk_base, uint64_t b) {
+    return BurstRange{seg_index[b], seg_index[b + 1], chunk_base[b], chunk_base[b + 1]};
+}
+
+__device__ __forceinline__ bool ts_burst_ok(const TcpBurstShape &s, const BurstRange &r,
+                                            uint64_t n_segments, uint64_t n_chunks) {
+    return s.valid && r.se >= r.sb && r.se - r.sb == s.S && r.se <= n_segments && r.ce >= r.cb &&
+           r.ce - r.cb == s.C && r.ce <= n_chunks;
+}
+
+// The chunk entries an invalid burst's index gives it, clipped to the table: [c0, c0 + cnt).
+__device__ __forceinline__ void ts_clip_chunks(const BurstRange &r, uint64_t n_chunks, uint64_t &c0,
+                                               uint64_t &cnt) {
+    c0 = r.cb < n_chunks ? r.cb : n_chunks;
+    cnt = r.ce >= r.cb ? r.ce - r.cb : 0u;
+    if (cnt > n_chunks - c0) cnt = n_chunks - c0;
+}
+
+__device__ __forceinline__ void ts_put_chunk(uint64_t *__restrict__ chunk_addr,
+                                             uint32_t *__restrict__ chunk_len, uint64_t c,
+                                             uint64_t n_chunks, uint64_t addr, uint32_t len) {
+    if (c < n_chunks) {  // (implied by ts_burst_ok; the table is never left whatever happens)
+        __builtin_nontemporal_store(addr, &chunk_addr[c]);
+        __builtin_nontemporal_store(len, &chunk_len[c]);
+    }
+}
+
+// Plan pass: segment i of the batch, owned by burst `b` (lane-varying or wave-uniform).
+__device__ __forceinline__ void ts_plan_segment(
+    const aipstack_tcp_burst *__restrict__ d, const BurstRange &r, uint64_t b, uint64_t i,
+    uint64_t n_segments, uint64_t n_chunks, uint64_t *__restrict__ chunk_addr,
+    uint32_t *__restrict__ chunk_len, uint64_t *__restrict__ chunk_index,
+    uint32_t *__restrict__ seeds, uint64_t *__restrict__ records) {
+    const TcpBurstShape s = tcp_burst_shape(*d);
+    const uint64_t k = i - r.sb;
+    uint32_t seed = 0;
+    uint64_t rec = b & kRecBurstMask, ci;
+    if (ts_burst_ok(s, r, n_segments, n_chunks)) {
+        const SegWords w = ts_segment(d, s, k);
+        const Template h = ts_template(d);
+        ci = r.cb + k + (k > s.straddle ? 1u : 0u);
+        const uint64_t len0 = d->data_len[0];
+        if (w.len != 0u) {
+            if (w.start + w.len <= len0) {
+                ts_put_chunk(chunk_addr, chunk_len, ci, n_chunks, d->data_addr[0] + w.start, w.len);
+            } else if (w.start >= len0) {
+                ts_put_chunk(chunk_addr, chunk_len, ci, n_chunks,
+                             d->data_addr[1] + (w.start - len0), w.len);
+            } else {  // the segment that straddles the piece boundary
+                const uint32_t first = (uint32_t)(len0 - w.start);
+                ts_put_chunk(chunk_addr, chunk_len, ci, n_chunks, d->data_addr[0] + w.start, first);
+                ts_put_chunk(chunk_addr, chunk_len, ci + 1, n_chunks, d->data_addr[1],
+                             w.len - first);
+            }
+        }
+        seed = ts_l4_seed(h, w);
+        rec |= (uint64_t)ts_ip_checksum(h, w) << 40 | kRecValid;
+    } else {
+        // its chunk entries are emptied by the burst loop below; the segments share them out
+        // in order so that the index stays non-decreasing
+        uint64_t c0, cnt;
+        ts_clip_chunks(r, n_chunks, c0, cnt);
+        ci = c0 + (k < cnt ? k : cnt);
+    }
+    __builtin_nontemporal_store(ci, &chunk_index[i]);
+    __builtin_nontemporal_store(seed, &seeds[i]);
+    __builtin_nontemporal_store(rec, &records[i]);
+}
+
+__global__ __launch_bounds__(kTsBlock) void tcpseg_plan_kernel(
+    const aipstack_tcp_burst *__restrict__ bursts, const uint64_t *__restrict__ seg_index,
+    const uint64_t *__restrict__ chunk_base, uint64_t n_bursts, uint64_t n_segments,
+    uint64_t n_chunks, uint64_t *__restrict__ chunk_addr, uint32_t *__restrict__ chunk_len,
+    uint64_t *__restrict__ chunk_index, uint32_t *__restrict__ seeds,
+    uint64_t *__restrict__ records) {
+    const uint64_t step = (uint64_t)gridDim.x * kTsBlock;
+    const uint32_t lane = threadIdx.x & (kTsWave - 1);
+    const uint64_t first = (uint64_t)blockIdx.x * kTsBlock + (threadIdx.x & ~(uint32_t)(kTsWave - 1));
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+        __builtin_nontemporal_store(n_chunks, &chunk_index[n_segments]);
+    for (uint64_t base = ts_uniform64(first); base < n_segments; base += step) {
+        // The wave's 64 segments mostly share one or two bursts: the owners of its first and
+        // last segment are found with wave-uniform searches, and each lane searches only
+        // between them (no step at all when they agree).
+        const uint64_t last = base + (kTsWave - 1) < n_segments ? base + (kTsWave - 1) : n_segments - 1;
+        const uint64_t j0 = ts_uniform64(ts_upper_bound(seg_index, 0, n_bursts + 1, base));
+        const uint64_t j1 = ts_uniform64(ts_upper_bound(seg_index, j0, n_bursts + 1, last));
+        const uint64_t i = base + lane;
+        if (i >= n_segments) continue;
+        if (j0 == j1 && j0 >= 1 && j0 <= n_bursts) {
+            const uint64_t b = j0 - 1;  // uniform: descriptor and index loads are shared
+            const BurstRange r = ts_range(seg_index, chunk_base, b);
+            if (r.sb <= base && last < r.se) {
+                ts_plan_segment(bursts + b, r, b, i, n_segments, n_chunks, chunk_addr, chunk_len,
+                                chunk_index, seeds, records);
+                continue;
+            }
+        }
+        const uint64_t j = ts_upper_bound(seg_index, j0, j1, i);
+        bool owned = j >= 1 && j <= n_bursts;
+        BurstRange r{0, 0, 0, 0};
+        if (owned) {
+            r = ts_range(seg_index, chunk_base, j - 1);
+            owned = r.sb <= i && i < r.se;
+        }
+        if (owned) {
+            ts_plan_segment(bursts + (j - 1), r, j - 1, i, n_segments, n_chunks, chunk_addr,
+                            chunk_len, chunk_index, seeds, records);
+        } else {  // the index gives the segment to no burst (it does not run from 0 to n)
+            __builtin_nontemporal_store(j == 0 ? (uint64_t)0 : n_chunks, &chunk_index[i]);
+            __builtin_nontemporal_store(0u, &seeds[i]);
+            __builtin_nontemporal_store((uint64_t)0, &records[i]);
+        }
+    }
+    // Bursts that break the contract: their chunk entries are emptied (length 0 at address 0),
+    // whether or not the index gives them a segment.
+    for (uint64_t b = (uint64_t)blockIdx.x * kTsBlock + threadIdx.x; b < n_bursts; b += step) {
+        const BurstRange r = ts_range(seg_index, chunk_base, b);
+        if (ts_burst_ok(tcp_burst_shape(bursts[b]), r, n_segments, n_chunks)) continue;
+        uint64_t c0, cnt;
+        ts_clip_chunks(r, n_chunks, c0, cnt);
+        for (uint64_t c = c0; c < c0 + cnt; ++c) ts_put_chunk(chunk_addr, chunk_len, c, n_chunks, 0, 0);
+    }
+}
+
+// Emit pass. LINES: hdr_stride == 64 and the ring starts on a 64-byte boundary.
+template <bool LINES>
+__global__ __launch_bounds__(kTsBlock) void tcpseg_emit_kernel(
+    const aipstack_tcp_burst *__restrict__ bursts, const uint64_t *__restrict__ seg_index,
+    const uint64_t *__restrict__ records, const uint16_t *__restrict__ sums, uint64_t hdr_base,
+    uint64_t hdr_stride, uint8_t *__restrict__ status, uint64_t n_segments) {
+    __shared__ u32x4 tile[LINES ? kTsBlock / kTsWave : 1][LINES ? kTsWave : 1][4];
+    const uint64_t step = (uint64_t)gridDim.x * kTsBlock;
+    const uint32_t lane = threadIdx.x & (kTsWave - 1);
+    const uint32_t wave = threadIdx.x >> 6;
+    const uint64_t first = (uint64_t)blockIdx.x * kTsBlock + (threadIdx.x & ~(uint32_t)(kTsWave - 1));
+    for (uint64_t base = ts_uniform64(first); base < n_segments; base += step) {
+        const uint64_t i = base + lane;
+        const bool active = i < n_segments;
+        const uint64_t rec = active ? __builtin_nontemporal_load(&records[i]) : 0u;
+        const bool valid = (rec & kRecValid) != 0u;
+        uint32_t o[16];
+#pragma unroll
+        for (int q = 0; q < 16; ++q) o[q] = 0u;
+        if (valid) {
+            const uint64_t b = rec & kRecBurstMask;
+            const aipstack_tcp_burst *__restrict__ d = bursts + b;
+            const TcpBurstShape s = tcp_burst_shape(*d);
+            const SegWords w = ts_segment(d, s, i - seg_index[b]);
+            const Template h = ts_template(d);
+            const uint32_t ipchk = (uint32_t)(rec >> 40) & 0xFFFFu;
+            // the chain's sum (seed (+) data, not inverted); a TCP checksum of 0 stays 0
+            const uint32_t l4chk = ~(uint32_t)__builtin_nontemporal_load(&sums[i]) & 0xFFFFu;
+#pragma unroll
+            for (int q = 0; q < 14; ++q) o[q] = h.t[q];
+            o[4] = ts_bswap16(w.total_len) | ts_bswap16(w.ident) << 16;
+            o[6] = ts_bswap16(ipchk) | (h.t[6] & 0xFFFF0000u);
+            o[9] = (h.t[9] & 0xFFFFu) | ts_bswap16(w.seq >> 16) << 16;
+            o[10] = ts_bswap16(w.seq & 0xFFFFu) | (h.t[10] & 0xFFFF0000u);
+            o[11] = (h.t[11] & 0xFFFFu) | ts_bswap16(w.offset_flags) << 16;
+            o[12] = (h.t[12] & 0xFFFFu) | ts_bswap16(l4chk) << 16;
+            o[13] = h.t[13] & 0xFFFFu;
+        }
+        if (active)
+            status[i] = (uint8_t)(valid ? AIPSTACK_RX_ACCEPT : AIPSTACK_TX_BURST_INVALID);
+        if constexpr (LINES) {
+            // slot `lane` into LDS, then store instruction r takes the quads of slots
+            // 16r .. 16r+15 in memory order: 64 lanes x 16 bytes = 1 KiB contiguous
+            const uint64_t ok = __builtin_amdgcn_ballot_w64(valid);
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                tile[wave][lane][q] = u32x4{o[4 * q], o[4 * q + 1], o[4 * q + 2], o[4 * q + 3]};
+            __builtin_amdgcn_wave_barrier();
+#pragma unroll
+            for (uint32_t r = 0; r < 4; ++r) {
+                const uint32_t slot = 16u * r + (lane >> 2), q = lane & 3u;
+                const u32x4 v = tile[wave][slot][q];
+                if ((ok >> slot) & 1ull)  // (a valid slot is below n_segments)
+                    __builtin_nontemporal_store(
+                        v, reinterpret_cast<g_line *>(hdr_base + (base + slot) * 64u + q * 16u));
+            }
+            __builtin_amdgcn_wave_barrier();
+        } else if (valid) {
+            const uint64_t P = hdr_base + i * hdr_stride;
+#pragma unroll
+            for (int q = 0; q < 3; ++q)
+                *reinterpret_cast<g_quad_any *>(P + 16u * q) =
+                    u32x4{o[4 * q], o[4 * q + 1], o[4 * q + 2], o[4 * q + 3]};
+            *reinterpret_cast<g_u32_any *>(P + 48u) = o[12];
+            *reinterpret_cast<g_u16_any *>(P + 52u) = (uint16_t)o[13];
+            const uint32_t end = hdr_stride < 64u ? (uint32_t)hdr_stride : 64u;
+            for (uint32_t z = AIPSTACK_TCP_SEGMENT_HEADER; z < end; ++z)
+                *reinterpret_cast<g_u8 *>(P + z) = 0u;
+        }
+    }
+}
+
+}  // namespace
+}  // namespace aipstack_amd
+
+using namespace aipstack_amd;
+
+extern "C" int aipstack_tcp_tx_segment(const aipstack_tcp_burst *d_bursts,
+                                       const uint64_t *d_seg_index, const uint64_t *d_chunk_base,
+                                       uint64_t n_bursts, uint64_t n_segments, uint64_t n_chunks,
+                                       void *d_hdr, uint64_t hdr_stride, uint64_t *d_chunk_addr,
+                                       uint32_t *d_chunk_len, uint64_t *d_chunk_index,
+                                       uint8_t *d_status, void *d_workspace,
+                                       uint64_t workspace_bytes, uint32_t flags, void *stream) {
+    if (n_segments == 0) return AIPSTACK_CHKSUM_OK;
+    int st = tcp_tx_segment_check_args(d_bursts, d_seg_index, d_chunk_base, n_bursts, n_segments,
+                                       n_chunks, d_hdr, hdr_stride, d_chunk_addr, d_chunk_len,
+                                       d_chunk_index, d_status, d_workspace, workspace_bytes);
+    if (st != AIPSTACK_CHKSUM_OK) return st;
+    const hipStream_t s = (hipStream_t)stream;
+    const int cus = device_cu_count(s);
+    if (cus <= 0) return AIPSTACK_CHKSUM_EHIP;
+    const uint64_t n = n_segments;
+    uint64_t *records = static_cast<uint64_t *>(d_workspace);
+    uint32_t *seeds = reinterpret_cast<uint32_t *>(records + n);
+    uint16_t *sums = reinterpret_cast<uint16_t *>(seeds + n);
+    const uint64_t want = (n + kTsBlock - 1) / kTsBlock, most = (uint64_t)cus * 64;
+    const unsigned blocks = (unsigned)(want < most ? want : most);
+    hipLaunchKernelGGL(tcpseg_plan_kernel, dim3(blocks), dim3(kTsBlock), 0, s, d_bursts,
+                       d_seg_index, d_chunk_base, n_bursts, n, n_chunks, d_chunk_addr, d_chunk_len,
+                       d_chunk_index, seeds, records);
+    st = check_hip(hipGetLastError());
+    if (st != AIPSTACK_CHKSUM_OK) return st;
+    st = aipstack_chksum_batch_chain(d_chunk_addr, d_chunk_len, d_chunk_index, seeds, n, sums,
+                                     flags & AIPSTACK_CHKSUM_JUST_WRITTEN, stream);
+    if (st != AIPSTACK_CHKSUM_OK) return st;
+    const uint64_t base = (uint64_t)(uintptr_t)d_hdr;
+    if (hdr_stride == 64u && (base & 63u) == 0u)
+        hipLaunchKernelGGL(tcpseg_emit_kernel<true>, dim3(blocks), dim3(kTsBlock), 0, s, d_bursts,
+                           d_seg_index, records, sums, base, hdr_stride, d_status, n);
+    else
+        hipLaunchKernelGGL(tcpseg_emit_kernel<false>, dim3(blocks), dim3(kTsBlock), 0, s, d_bursts,
+                           d_seg_index, records, sums, base, hdr_stride, d_status, n);
+    return check_hip(hipGetLastError());
+}

@@ -261,6 +261,101 @@ int aipstack_chksum_tx_fill_hsplit(void *d_hdr, uint64_t hdr_stride, const uint3
                                    uint8_t *d_status, void *d_workspace,
                                    uint64_t workspace_bytes, uint32_t flags, void *stream);
 
+/* ---- TCP burst segmentation: headers, chunk table and checksums of a data burst -------- */
+
+/* The reference sends a burst of one connection's data as a loop: pcb_output_active ->
+ * pcb_output_segment -> PcbOutputHelper::sendSegment -> IpStack::sendIp4DgramFast
+ * (tcp/IpTcpProto_output.h:1056-1120, 1218-1335, ip/IpStack.h:564-663). What is common to the
+ * burst is prepared once (prepareCommon, prepareSendIp4Dgram: ports, ack, window, addresses,
+ * both partial checksum States); per segment only seq_num, the PSH / FIN bits, tcp_len, the
+ * IPv4 total length, ident (m_next_id++) and the two checksums change. This is that loop for a
+ * batch of bursts: the host hands over one descriptor per burst, the GPU emits every segment's
+ * complete 54-byte frame header, the chunk table of its data and both checksums, in the layout
+ * aipstack_chksum_tx_fill_hsplit, aipstack_chksum_batch_chain and a scatter-gather sender take.
+ * Deciding what to send (window, retransmission, the TCP state machine) stays with the host. */
+#define AIPSTACK_TCP_SEGMENT_HEADER 54u   /* Ethernet 14 + IPv4 20 (IHL 5) + TCP 20 (offset 5) */
+#define AIPSTACK_TCP_BURST_FIN 1u         /* burst flag: the last segment carries FIN|PSH */
+#define AIPSTACK_TX_BURST_INVALID 10      /* per-segment status: its burst breaks the contract */
+
+typedef struct aipstack_tcp_burst {       /* 96 bytes, 8-byte aligned, host-made */
+    uint64_t data_addr[2];  /* DEVICE addresses of the burst's bytes: a range of the circular send
+                               buffer is at most two pieces (utils/TcpRingBufferUtils.h:51,113);
+                               piece 1 follows piece 0; any alignment */
+    uint32_t data_len[2];   /* bytes in each piece; their sum D must fit 32 bits */
+    uint32_t seq;           /* sequence number of the burst's first byte (snd_una + offset, :1102) */
+    uint32_t psh_offset;    /* snd_psh_index relative to the burst start: PSH on the segment with
+                               start < psh_offset <= start + len (:1096-1099); 0 = none */
+    uint16_t mss;           /* data bytes per segment: 1 .. 65535 - 40 */
+    uint16_t ip_id;         /* Ident of segment 0; segment k gets ip_id + k mod 2^16 (IpStack.h:653) */
+    uint8_t  flags;         /* AIPSTACK_TCP_BURST_FIN */
+    uint8_t  reserved[3];   /* 0 */
+    uint8_t  hdr[56];       /* template, first 54 bytes: the frame header as prepareCommon and
+                               prepareSendIp4Dgram leave it */
+} aipstack_tcp_burst;
+
+/* Segments of a burst (:1069-1090), D = data_len[0] + data_len[1]: S = ceil(D / mss) when
+ * D > 0; S = 1 when D == 0 and FIN is set (a segment without data); else S = 0 (legal, produces
+ * nothing). Segment k: start = k*mss, len = min(mss, D - start); sequence number seq + start
+ * (mod 2^32); offset_flags = Tcp4EncodeOffset(5) | Ack, Psh by the psh_offset rule, Fin|Psh on
+ * the last segment of a FIN burst; IPv4 total length 40 + len; ident ip_id + k; the IPv4 header
+ * checksum as sendIp4DgramFast computes it; the TCP checksum as sendSegment does (pseudo-header,
+ * the 20 header bytes, the data chain; a computed 0 stays 0x0000, 0 -> 0xFFFF is UDP's rule).
+ * Template: the IPv4 total length, ident and header checksum and the TCP seq, offset/flags and
+ * checksum are ignored and overwritten; every other byte (MACs, EtherType, version/IHL/DSCP,
+ * flags/fragment offset, TTL, protocol, addresses, ports, ack, window, urgent pointer) is
+ * copied. Data: the bytes [start, start + len) of the two-piece range -- one chunk, two for the
+ * one segment that straddles the piece boundary, none for a FIN-only segment.
+ *
+ * Burst contract: mss >= 1; 40 + mss <= 65535; D < 2^32; reserved == 0; no flag bit but FIN;
+ * template EtherType 0x0800, version/IHL 0x45, protocol 6; seg_index[b+1] - seg_index[b] == S
+ * and chunk_base[b+1] - chunk_base[b] == the burst's chunk count. */
+
+/* Host side, no GPU: segment and chunk counts of each burst as running sums (n_bursts + 1
+ * entries each, starting at 0); _EINVAL if a burst breaks the contract above (or for a null
+ * pointer, n_bursts > 2^40). */
+int aipstack_tcp_burst_layout(const aipstack_tcp_burst *h_bursts, uint64_t n_bursts,
+                              uint64_t *h_seg_index, uint64_t *h_chunk_base);
+
+uint64_t aipstack_tcp_tx_segment_workspace_bytes(uint64_t n_segments);   /* <= 16*n + 256 */
+
+/* The batch. d_bursts, d_seg_index, d_chunk_base: the descriptors and the two running sums of
+ * aipstack_tcp_burst_layout, in DEVICE memory (non-decreasing, from 0 to n_segments / n_chunks).
+ * Segment i is the k-th segment of the burst b that holds it (seg_index[b] <= i <
+ * seg_index[b+1], k = i - seg_index[b]). The call leaves:
+ *   - its 54 header bytes at d_hdr + i*hdr_stride, the slot's bytes [54, min(hdr_stride, 64))
+ *     written as 0 (a 64-byte ring is stored in whole lines), bytes past 64 untouched; slots
+ *     are written once, whole, and never read;
+ *   - a compact chunk table in the form and contract of aipstack_chksum_batch_chain (no empty
+ *     chunks; d_chunk_index[n_segments] = n_chunks; n_chunks entries of d_chunk_addr /
+ *     d_chunk_len, n_segments + 1 of d_chunk_index). Within a burst, segment k's first chunk
+ *     is chunk_base[b] + k, plus 1 if k lies after the straddling segment;
+ *   - d_status[i] = AIPSTACK_RX_ACCEPT.
+ * The bytes are what the reference loop produces, and what aipstack_chksum_tx_fill_hsplit
+ * leaves when run on the same headers with both fields zeroed.
+ * A burst that breaks the contract: every segment the caller's index gives it gets
+ * AIPSTACK_TX_BURST_INVALID, its slots stay untouched, and its chunk entries are written with
+ * length 0 at address 0 (harmless to the chained batch). Whatever the descriptors hold, only
+ * the n_segments slots, the n_chunks entries, the index, d_status and the workspace are
+ * written.
+ *
+ * Three stream-ordered passes through the caller's workspace (8-byte aligned, at least
+ * aipstack_tcp_tx_segment_workspace_bytes(n_segments) bytes, free again once the stream passes
+ * the call): a plan pass (owner search, validation, chunk table, the L4 seed and the IPv4
+ * checksum as arithmetic on header words), the chained batch over the table just written, an
+ * emit pass that builds and stores the slots. Never allocates or synchronises; can be captured
+ * into a graph and repeated (outputs depend on inputs only). flags:
+ * AIPSTACK_CHKSUM_JUST_WRITTEN (the payload read); other bits are ignored. _EINVAL before any
+ * work for a null pointer, hdr_stride < 54, n_bursts / n_segments / n_chunks above 2^40, a
+ * short or misaligned workspace; n_segments == 0 is a no-op. */
+int aipstack_tcp_tx_segment(const aipstack_tcp_burst *d_bursts, const uint64_t *d_seg_index,
+                            const uint64_t *d_chunk_base, uint64_t n_bursts,
+                            uint64_t n_segments, uint64_t n_chunks,
+                            void *d_hdr, uint64_t hdr_stride,
+                            uint64_t *d_chunk_addr, uint32_t *d_chunk_len,
+                            uint64_t *d_chunk_index, uint8_t *d_status,
+                            void *d_workspace, uint64_t workspace_bytes,
+                            uint32_t flags, void *stream);
+
 /* ---- 3. host-memory streaming engine ----------------------------------------------- */
 
 /* The reference's packet path starts and ends in host memory (TAP read()/write(),
