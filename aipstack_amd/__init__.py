@@ -59,6 +59,17 @@ from .chksum import (  # noqa: E402
     TcpSegments,
     tcp_burst_layout,
     tcp_tx_segment,
+    AIPSTACK_RX_DROP_TCP_OFFSET,
+    AIPSTACK_TCP_NO_PCB,
+    AIPSTACK_TCP_OPT_MSS,
+    AIPSTACK_TCP_OPT_WND_SCALE,
+    AIPSTACK_TCP_SEG_VALID,
+    TCP_PCB_KEY_DTYPE,
+    TCP_RX_SEG_DTYPE,
+    TcpRxParsed,
+    tcp_pcb_table_sort,
+    tcp_rx_parse,
+    tcp_rx_parse_slotted,
 )
 
 LIB_PATH = _lib.LIB_PATH
@@ -77,4 +88,7 @@ __all__ = [
     "tx_fill_header_split",
     "AIPSTACK_TCP_BURST_FIN", "AIPSTACK_TCP_SEGMENT_HEADER", "AIPSTACK_TX_BURST_INVALID",
     "TCP_BURST_DTYPE", "TcpSegments", "tcp_burst_layout", "tcp_tx_segment",
+    "AIPSTACK_RX_DROP_TCP_OFFSET", "AIPSTACK_TCP_NO_PCB", "AIPSTACK_TCP_OPT_MSS",
+    "AIPSTACK_TCP_OPT_WND_SCALE", "AIPSTACK_TCP_SEG_VALID", "TCP_PCB_KEY_DTYPE", "TCP_RX_SEG_DTYPE",
+    "TcpRxParsed", "tcp_pcb_table_sort", "tcp_rx_parse", "tcp_rx_parse_slotted",
 ]

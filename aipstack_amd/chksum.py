@@ -1374,6 +1374,147 @@ def tcp_tx_segment(bursts, seg_index, chunk_base, *, hdr_stride: int = 64, heade
     return res
 
 
+AIPSTACK_RX_DROP_TCP_OFFSET = 11    # tcp_rx_parse: TCP checksum good, data offset out of range
+AIPSTACK_TCP_NO_PCB = 0xFFFFFFFF
+AIPSTACK_TCP_OPT_MSS = 1            # = TcpOptionFlags::Mss
+AIPSTACK_TCP_OPT_WND_SCALE = 2      # = TcpOptionFlags::WndScale
+AIPSTACK_TCP_SEG_VALID = 0x80
+
+# ``aipstack_tcp_rx_seg`` (chksum.h): one parsed TCP segment, host byte order.
+TCP_RX_SEG_DTYPE = np.dtype({
+    "names": ["remote_addr", "local_addr", "remote_port", "local_port", "seq_num", "ack_num",
+              "flags", "window_size", "data_off", "data_len", "mss", "wnd_scale", "opts"],
+    "formats": ["<u4", "<u4", "<u2", "<u2", "<u4", "<u4", "<u2", "<u2", "<u2", "<u2", "<u2", "u1",
+                "u1"],
+    "offsets": [0, 4, 8, 10, 12, 16, 20, 22, 24, 26, 28, 30, 31],
+    "itemsize": 32,
+})
+# ``aipstack_tcp_pcb_key`` (chksum.h): one entry of the PCB table.
+TCP_PCB_KEY_DTYPE = np.dtype({
+    "names": ["local_addr", "remote_addr", "local_port", "remote_port", "cookie"],
+    "formats": ["<u4", "<u4", "<u2", "<u2", "<u4"],
+    "offsets": [0, 4, 8, 10, 12],
+    "itemsize": 16,
+})
+assert TCP_RX_SEG_DTYPE.itemsize == 32 and TCP_PCB_KEY_DTYPE.itemsize == 16
+
+
+def tcp_pcb_table_sort(keys):
+    """Host side of :func:`tcp_rx_parse` (``aipstack_tcp_pcb_table_sort``, no GPU): a copy of
+    ``keys`` (a ``TCP_PCB_KEY_DTYPE`` array) sorted into the order of the reference's
+    ``CompareKeys`` (remote_port, remote_addr, local_port, local_addr), the order the lookup
+    searches. Raises :class:`ChksumError` (``AIPSTACK_CHKSUM_EINVAL``) for a duplicate key or a
+    cookie equal to ``AIPSTACK_TCP_NO_PCB``."""
+    k = np.array(keys, dtype=TCP_PCB_KEY_DTYPE).reshape(-1)
+    _check(_lib.load().aipstack_tcp_pcb_table_sort(k.ctypes.data if k.size else None, k.size),
+           "aipstack_tcp_pcb_table_sort")
+    return k
+
+
+class TcpRxParsed:
+    """What :func:`tcp_rx_parse` leaves (device tensors): ``verdict`` (uint8, n), ``segs`` (uint8,
+    n * 32 bytes: n ``aipstack_tcp_rx_seg`` records) and ``pcb`` (int32, n: the cookies, bit
+    pattern of ``AIPSTACK_TCP_NO_PCB`` = -1 where no PCB matches)."""
+
+    def __init__(self, verdict, segs, pcb):
+        self.verdict, self.segs, self.pcb = verdict, segs, pcb
+
+    @property
+    def n(self) -> int:
+        return self.verdict.numel()
+
+    def segs_numpy(self) -> np.ndarray:
+        """The records on the host as a ``TCP_RX_SEG_DTYPE`` array (synchronises)."""
+        return self.segs[:self.n * 32].cpu().numpy().view(TCP_RX_SEG_DTYPE)
+
+    def pcb_numpy(self) -> np.ndarray:
+        """The cookies on the host as uint32 (synchronises)."""
+        return self.pcb[:self.n].cpu().numpy().view(np.uint32)
+
+
+def _rx_parse_outputs(n, frames, verdict, segs, pcb):
+    torch = _torch()
+    verdict = _u8_out(verdict, n, frames)
+    if segs is None:
+        segs = torch.empty(n * 32, dtype=torch.uint8, device=frames.device)
+    else:
+        _require_device(segs, "segs")
+        if segs.element_size() != 1 or segs.numel() < n * 32:
+            raise ValueError("segs must be a uint8 device tensor of at least n * 32 bytes")
+        _same_device(segs, frames, "segs and frames")
+    if pcb is None:
+        pcb = torch.empty(n, dtype=torch.int32, device=frames.device)
+    else:
+        _require_device(pcb, "pcb")
+        if pcb.element_size() != 4 or pcb.numel() < n:
+            raise ValueError("pcb must be an int32/uint32 device tensor with >= n elements")
+        _same_device(pcb, frames, "pcb and frames")
+    return verdict, segs, pcb
+
+
+def _rx_parse_table(pcbs, frames):
+    """(pointer, entries, tensor to keep alive) of the PCB table: None, a device uint8 tensor of
+    whole 16-byte entries, or a host ``TCP_PCB_KEY_DTYPE`` array (uploaded here)."""
+    torch = _torch()
+    if pcbs is None:
+        return 0, 0, None
+    if not hasattr(pcbs, "data_ptr"):
+        k = np.ascontiguousarray(pcbs, dtype=TCP_PCB_KEY_DTYPE).reshape(-1)
+        if k.size == 0:
+            return 0, 0, None
+        pcbs = torch.from_numpy(k.view(np.uint8).copy()).to(frames.device)
+    _require_device(pcbs, "pcbs")
+    _same_device(pcbs, frames, "pcbs and frames")
+    nbytes = pcbs.numel() * pcbs.element_size()
+    if nbytes % 16:
+        raise ValueError("pcbs must hold whole 16-byte entries")
+    return (pcbs.data_ptr() if nbytes else 0), nbytes // 16, pcbs
+
+
+def tcp_rx_parse(frames, offsets, pcbs=None, *, verdict=None, segs=None, pcb=None, stream=None):
+    """Rx verify plus the TCP parse on the GPU (``aipstack_tcp_rx_parse``): frame i =
+    ``frames[offsets[i]:offsets[i+1]]``. Per frame the verdict of :func:`rx_verify` (an accepted
+    TCP frame whose data offset is out of range becomes ``AIPSTACK_RX_DROP_TCP_OFFSET``), for an
+    accepted TCP frame the ``aipstack_tcp_rx_seg`` record (segment fields, where the data lies,
+    the MSS / window-scale options as the reference's ``ParseTcpOptions`` reads them), and the
+    cookie of its PCB in ``pcbs``: a table sorted by :func:`tcp_pcb_table_sort`, a host
+    ``TCP_PCB_KEY_DTYPE`` array (uploaded on the launch stream) or a device uint8 tensor already
+    resident; ``None`` = no table. Returns a :class:`TcpRxParsed`."""
+    _require_device(frames, "frames")
+    _require_offsets(offsets)
+    _same_device(frames, offsets, "frames and offsets")
+    n = max(offsets.numel() - 1, 0)
+    verdict, segs, pcb = _rx_parse_outputs(n, frames, verdict, segs, pcb)
+    launch_stream = _launch_stream(stream, frames.device)
+    with _torch().cuda.stream(launch_stream):  # an upload is ordered before the call
+        tp, tn, keep = _rx_parse_table(pcbs, frames)
+    _check(_lib.load().aipstack_tcp_rx_parse(
+        frames.data_ptr(), offsets.data_ptr(), n, tp, tn, verdict.data_ptr(), segs.data_ptr(),
+        pcb.data_ptr(), _stream_handle(launch_stream)), "aipstack_tcp_rx_parse")
+    if keep is not None and keep is not pcbs:
+        keep.record_stream(launch_stream)
+    return TcpRxParsed(verdict, segs, pcb)
+
+
+def tcp_rx_parse_slotted(frames, slot_stride: int, lens, pcbs=None, *, verdict=None, segs=None,
+                         pcb=None, stream=None):
+    """:func:`tcp_rx_parse` on a ring of frame slots (frame i = the lens[i] bytes at
+    ``frames[i*slot_stride:]``, as :func:`rx_verify_slotted`)."""
+    _require_device(frames, "frames")
+    n = _require_lens(lens, frames.numel() * frames.element_size(), slot_stride, frames)
+    verdict, segs, pcb = _rx_parse_outputs(n, frames, verdict, segs, pcb)
+    launch_stream = _launch_stream(stream, frames.device)
+    with _torch().cuda.stream(launch_stream):
+        tp, tn, keep = _rx_parse_table(pcbs, frames)
+    _check(_lib.load().aipstack_tcp_rx_parse_slotted(
+        frames.data_ptr(), slot_stride, lens.data_ptr(), n, tp, tn, verdict.data_ptr(),
+        segs.data_ptr(), pcb.data_ptr(), _stream_handle(launch_stream)),
+        "aipstack_tcp_rx_parse_slotted")
+    if keep is not None and keep is not pcbs:
+        keep.record_stream(launch_stream)
+    return TcpRxParsed(verdict, segs, pcb)
+
+
 class SplitFrames:
     """What :func:`split_frames` returns (host arrays): ``headers`` (n slots of ``hdr_stride``
     bytes), ``hdr_lens`` (uint32), ``payload`` (uint8, every chunk's bytes) and ``chunks``
@@ -1517,7 +1658,7 @@ def apply_tx_records(frames: np.ndarray, offsets: np.ndarray, records: np.ndarra
 
 RX_VERDICTS = {0: "NOT_IP4", 1: "DROP_IP_MALFORMED", 2: "DROP_IP_CHKSUM", 3: "FRAGMENT",
                4: "DROP_L4_MALFORMED", 5: "DROP_L4_CHKSUM", 6: "ACCEPT",
-               7: "ACCEPT_NO_CHKSUM", 8: "ACCEPT_OTHER"}
+               7: "ACCEPT_NO_CHKSUM", 8: "ACCEPT_OTHER", 11: "DROP_TCP_OFFSET"}
 
 
 def flatten_chains(refs, host_base: np.ndarray, device_base: int):

@@ -1,0 +1,205 @@
+// aipstack_amd -- TCP Rx parse: what the reference does with a TCP datagram between its
+// checksum check and the call of pcb_input (tcp/IpTcpProto_input.h:81-130) for a batch of
+// frames: the TcpSegMeta fields, the data offset bound, the options (ParseTcpOptions,
+// tcp/TcpOptions.h:63-125) and the PCB lookup (find_pcb, tcp/IpTcpProto.h:806-820). Two
+// stream-ordered launches:
+//   1. Rx verify (aipstack_chksum_rx_verify / _slotted), unchanged, into d_verdict;
+//   2. tcprx_parse_kernel, one frame per lane: the verdict, and only of a frame accepted as TCP
+//      its header bytes, read as dwords at the frame's own byte alignment and only inside the
+//      frame (tcp_rx_build, tcprx_common.h: the fixed fields, then the options as ten fixed
+//      dwords fed to a byte machine -- no array indexed by a run-time position, no scratch);
+//      a binary search of the sorted table, one 16-byte entry per step, every index inside
+//      [0, n_pcbs); the 32-byte record, the cookie, and the verdict byte where it changes.
+//      Records of a 16-byte aligned d_segs go through LDS so that each of the wave's two store
+//      instructions covers 1 KiB of contiguous memory; otherwise 8-byte stores per lane.
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "aipstack_amd/chksum.h"
+#include "chksum_internal.h"
+#include "tcprx_common.h"
+
+namespace aipstack_amd {
+namespace {
+
+constexpr int kRxBlock = 256;
+constexpr int kRxWave = 64;
+
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+#define AIPSTACK_RXP_GLOBAL __attribute__((address_space(1)))
+typedef AIPSTACK_RXP_GLOBAL u32x4 g_line;
+typedef AIPSTACK_RXP_GLOBAL u32x2 g_pair;
+typedef const AIPSTACK_RXP_GLOBAL uint32_t g_cu32_any __attribute__((aligned(1)));
+typedef const AIPSTACK_RXP_GLOBAL u32x4 g_entry __attribute__((aligned(8)));
+
+__device__ __forceinline__ uint64_t rxp_uniform64(uint64_t v) {
+    return ((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(v >> 32)) << 32) |
+           __builtin_amdgcn_readfirstlane((uint32_t)v);
+}
+
+// Frame i's start address and length, as Rx verify takes them.
+struct CsrFrames {
+    uint64_t base;
+    const uint64_t *offsets;
+    __device__ __forceinline__ void frame(uint64_t i, uint64_t &S, uint32_t &len) const {
+        const uint64_t a = offsets[i], b = offsets[i + 1];
+        S = base + a;
+        const uint64_t l = b - a;  // b < a, or over 65535 bytes: outside the contract, no read
+        len = l > (uint64_t)AIPSTACK_CHKSUM_MAX_LEN ? 0u : (uint32_t)l;
+    }
+};
+
+struct SlotFrames {
+    uint64_t base, stride;
+    const uint32_t *lens;
+    uint32_t cap;  // min(stride, 65535), as verify clamps a slot's length
+    __device__ __forceinline__ void frame(uint64_t i, uint64_t &S, uint32_t &len) const {
+        S = base + i * stride;
+        const uint32_t l = lens[i];
+        len = l < cap ? l : cap;
+    }
+};
+
+// The little-endian dword at frame bytes [off, off + 4): a load at the frame's own alignment.
+struct FrameLoad {
+    uint64_t S;
+    __device__ __forceinline__ uint32_t operator()(uint32_t off) const {
+        return *reinterpret_cast<g_cu32_any *>(S + off);
+    }
+};
+
+// The cookie of the entry equal to `key` in the table sorted by tcp_pcb_key_compare. Every
+// entry read has an index in [lo, hi) within [0, n_pcbs), whatever the table holds; the range
+// shrinks by at least one entry per step.
+__device__ __forceinline__ uint32_t rxp_lookup(const aipstack_tcp_pcb_key *__restrict__ pcbs,
+                                               uint64_t n_pcbs, const aipstack_tcp_pcb_key &key) {
+    uint64_t lo = 0, hi = n_pcbs;
+    while (lo < hi) {
+        const uint64_t mid = lo + ((hi - lo) >> 1);
+        const u32x4 e = *reinterpret_cast<g_entry *>((uint64_t)(uintptr_t)pcbs + mid * 16u);
+        aipstack_tcp_pcb_key k;
+        k.local_addr = e.x;
+        k.remote_addr = e.y;
+        k.local_port = (uint16_t)(e.z & 0xFFFFu);
+        k.remote_port = (uint16_t)(e.z >> 16);
+        const int c = tcp_pcb_key_compare(k, key);
+        if (c == 0) return e.w;
+        if (c < 0) lo = mid + 1;
+        else hi = mid;
+    }
+    return AIPSTACK_TCP_NO_PCB;
+}
+
+// LINES: d_segs is 16-byte aligned.
+template <class Frames, bool LINES>
+__global__ __launch_bounds__(kRxBlock) void tcprx_parse_kernel(
+    const Frames fr, uint64_t n, const aipstack_tcp_pcb_key *__restrict__ pcbs, uint64_t n_pcbs,
+    uint8_t *__restrict__ verdict, uint64_t segs, uint32_t *__restrict__ pcb) {
+    __shared__ u32x4 tile[LINES ? kRxBlock / kRxWave : 1][LINES ? kRxWave : 1][2];
+    const uint64_t step = (uint64_t)gridDim.x * kRxBlock;
+    const uint32_t lane = threadIdx.x & (kRxWave - 1);
+    const uint32_t wave = threadIdx.x >> 6;
+    const uint64_t first = (uint64_t)blockIdx.x * kRxBlock + (threadIdx.x & ~(uint32_t)(kRxWave - 1));
+    for (uint64_t base = rxp_uniform64(first); base < n; base += step) {
+        const uint64_t i = base + lane;
+        const bool active = i < n;
+        uint32_t w[8];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) w[q] = 0u;
+        uint32_t cookie = AIPSTACK_TCP_NO_PCB;
+        if (active && verdict[i] == AIPSTACK_RX_ACCEPT) {
+            uint64_t S;
+            uint32_t len;
+            fr.frame(i, S, len);
+            aipstack_tcp_pcb_key key;
+            uint32_t r[8];
+            const int res = tcp_rx_build(FrameLoad{S}, len, r, key);
+            if (res == kTcpRxValid) {
+#pragma unroll
+                for (int q = 0; q < 8; ++q) w[q] = r[q];
+                cookie = rxp_lookup(pcbs, n_pcbs, key);
+            } else if (res == kTcpRxBadOffset) {
+                verdict[i] = (uint8_t)AIPSTACK_RX_DROP_TCP_OFFSET;
+            }
+        }
+        if (active) __builtin_nontemporal_store(cookie, &pcb[i]);
+        if constexpr (LINES) {
+            // record `lane` into LDS, then store instruction r takes the quads of records
+            // 32r .. 32r+31 in memory order: 64 lanes x 16 bytes = 1 KiB contiguous
+            tile[wave][lane][0] = u32x4{w[0], w[1], w[2], w[3]};
+            tile[wave][lane][1] = u32x4{w[4], w[5], w[6], w[7]};
+            __builtin_amdgcn_wave_barrier();
+#pragma unroll
+            for (uint32_t r = 0; r < 2; ++r) {
+                const uint32_t rec = 32u * r + (lane >> 1), q = lane & 1u;
+                const u32x4 v = tile[wave][rec][q];
+                if (base + rec < n)
+                    __builtin_nontemporal_store(
+                        v, reinterpret_cast<g_line *>(segs + (base + rec) * 32u + q * 16u));
+            }
+            __builtin_amdgcn_wave_barrier();
+        } else if (active) {
+#pragma unroll
+            for (uint32_t q = 0; q < 4; ++q)
+                __builtin_nontemporal_store(
+                    u32x2{w[2 * q], w[2 * q + 1]},
+                    reinterpret_cast<g_pair *>(segs + i * 32u + q * 8u));
+        }
+    }
+}
+
+template <class Frames>
+int launch_parse(const Frames &fr, uint64_t n, const aipstack_tcp_pcb_key *d_pcbs, uint64_t n_pcbs,
+                 uint8_t *d_verdict, aipstack_tcp_rx_seg *d_segs, uint32_t *d_pcb, hipStream_t s) {
+    const int cus = device_cu_count(s);
+    if (cus <= 0) return AIPSTACK_CHKSUM_EHIP;
+    const uint64_t want = (n + kRxBlock - 1) / kRxBlock, most = (uint64_t)cus * 64;
+    const unsigned blocks = (unsigned)(want < most ? want : most);
+    const uint64_t segs = (uint64_t)(uintptr_t)d_segs;
+    if ((segs & 15u) == 0u)
+        hipLaunchKernelGGL((tcprx_parse_kernel<Frames, true>), dim3(blocks), dim3(kRxBlock), 0, s, fr,
+                           n, d_pcbs, n_pcbs, d_verdict, segs, d_pcb);
+    else
+        hipLaunchKernelGGL((tcprx_parse_kernel<Frames, false>), dim3(blocks), dim3(kRxBlock), 0, s,
+                           fr, n, d_pcbs, n_pcbs, d_verdict, segs, d_pcb);
+    return check_hip(hipGetLastError());
+}
+
+}  // namespace
+}  // namespace aipstack_amd
+
+using namespace aipstack_amd;
+
+extern "C" int aipstack_tcp_rx_parse(const void *d_base, const uint64_t *d_offsets, uint64_t n,
+                                     const aipstack_tcp_pcb_key *d_pcbs, uint64_t n_pcbs,
+                                     uint8_t *d_verdict, aipstack_tcp_rx_seg *d_segs,
+                                     uint32_t *d_pcb, void *stream) {
+    if (n == 0) return AIPSTACK_CHKSUM_OK;
+    int st = tcp_rx_parse_check_args(d_base, d_offsets, false, 0, n, d_pcbs, n_pcbs, d_verdict,
+                                     d_segs, d_pcb);
+    if (st != AIPSTACK_CHKSUM_OK) return st;
+    st = aipstack_chksum_rx_verify(d_base, d_offsets, n, d_verdict, stream);
+    if (st != AIPSTACK_CHKSUM_OK) return st;
+    const CsrFrames fr{(uint64_t)(uintptr_t)d_base, d_offsets};
+    return launch_parse(fr, n, d_pcbs, n_pcbs, d_verdict, d_segs, d_pcb, (hipStream_t)stream);
+}
+
+extern "C" int aipstack_tcp_rx_parse_slotted(const void *d_base, uint64_t slot_stride,
+                                             const uint32_t *d_len, uint64_t n,
+                                             const aipstack_tcp_pcb_key *d_pcbs, uint64_t n_pcbs,
+                                             uint8_t *d_verdict, aipstack_tcp_rx_seg *d_segs,
+                                             uint32_t *d_pcb, void *stream) {
+    if (n == 0) return AIPSTACK_CHKSUM_OK;
+    int st = tcp_rx_parse_check_args(d_base, d_len, true, slot_stride, n, d_pcbs, n_pcbs,
+                                     d_verdict, d_segs, d_pcb);
+    if (st != AIPSTACK_CHKSUM_OK) return st;
+    st = aipstack_chksum_rx_verify_slotted(d_base, slot_stride, d_len, n, d_verdict, stream);
+    if (st != AIPSTACK_CHKSUM_OK) return st;
+    const uint32_t cap = (uint32_t)(slot_stride < AIPSTACK_CHKSUM_MAX_LEN ? slot_stride
+                                                                           : AIPSTACK_CHKSUM_MAX_LEN);
+    const SlotFrames fr{(uint64_t)(uintptr_t)d_base, slot_stride, d_len, cap};
+    return launch_parse(fr, n, d_pcbs, n_pcbs, d_verdict, d_segs, d_pcb, (hipStream_t)stream);
+}

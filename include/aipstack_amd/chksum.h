@@ -356,6 +356,79 @@ int aipstack_tcp_tx_segment(const aipstack_tcp_burst *d_bursts, const uint64_t *
                             void *d_workspace, uint64_t workspace_bytes,
                             uint32_t flags, void *stream);
 
+/* ---- TCP Rx parse: segment metadata, options and PCB lookup of a batch of frames -------- */
+
+/* What the reference does with a TCP datagram once its checksum is good, up to the call of
+ * pcb_input (tcp/IpTcpProto_input.h:81-130): read the six TcpSegMeta fields (:81-90,
+ * tcp/TcpMiscUtils.h:40-48), bound the data offset and cut the options from the data
+ * (:103-122), parse the MSS and window-scale options (ParseTcpOptions, tcp/TcpOptions.h:63-125)
+ * and find the PCB by address tuple (find_pcb, tcp/IpTcpProto.h:806-820, ordered by
+ * TcpPcbKeyCompare::CompareKeys, tcp/TcpPcbKey.h:50-86) -- for a batch of frames in device
+ * memory. The host's Rx loop becomes "for each record with a PCB: pcb_input(pcb, meta, data)".
+ * The TCP state machine, listeners, RST replies and the local-address / unicast-source checks
+ * (they need interface state) stay with the host. */
+#define AIPSTACK_RX_DROP_TCP_OFFSET 11      /* TCP checksum good, data offset outside
+                                               [20, datagram length] (IpTcpProto_input.h:108-116) */
+#define AIPSTACK_TCP_NO_PCB 0xFFFFFFFFu
+#define AIPSTACK_TCP_OPT_MSS 1u             /* = TcpOptionFlags::Mss      */
+#define AIPSTACK_TCP_OPT_WND_SCALE 2u       /* = TcpOptionFlags::WndScale */
+#define AIPSTACK_TCP_SEG_VALID 0x80u
+
+typedef struct aipstack_tcp_rx_seg {        /* 32 bytes, host byte order */
+    uint32_t remote_addr, local_addr;       /* IPv4 source, destination (Ip4Addr::value()) */
+    uint16_t remote_port, local_port;       /* TCP source, destination port */
+    uint32_t seq_num, ack_num;
+    uint16_t flags;                         /* the raw OffsetFlags word */
+    uint16_t window_size;
+    uint16_t data_off;                      /* first data byte, from the frame start: 14 + 4*IHL + 4*offset */
+    uint16_t data_len;                      /* IPv4 total length - 4*IHL - 4*offset (not the frame's length:
+                                               Ethernet padding is not data) */
+    uint16_t mss;                           /* valid with _OPT_MSS, else 0 */
+    uint8_t  wnd_scale;                     /* valid with _OPT_WND_SCALE, else 0 */
+    uint8_t  opts;                          /* _OPT_* | _SEG_VALID */
+} aipstack_tcp_rx_seg;
+
+typedef struct aipstack_tcp_pcb_key {       /* 16 bytes */
+    uint32_t local_addr, remote_addr;
+    uint16_t local_port, remote_port;
+    uint32_t cookie;                        /* the caller's PCB handle; != AIPSTACK_TCP_NO_PCB */
+} aipstack_tcp_pcb_key;
+
+/* Host side, no GPU: sorts the table in place into the order of CompareKeys (ascending by
+ * remote_port, then remote_addr, then local_port, then local_addr), the order the lookup
+ * searches. _EINVAL for a null pointer with n > 0, n > 2^40, a duplicate key or a cookie equal
+ * to AIPSTACK_TCP_NO_PCB; the array is then left as a permutation of its input. */
+int aipstack_tcp_pcb_table_sort(aipstack_tcp_pcb_key *h_keys, uint64_t n);
+
+/* The batch (frames as aipstack_chksum_rx_verify / _rx_verify_slotted take them, under the same
+ * offsets, span and slot contracts). Per frame i:
+ *   - d_verdict[i]: what Rx verify gives, except that a frame it accepts as TCP
+ *     (AIPSTACK_RX_ACCEPT, protocol 6) whose data offset 4*(flags >> 12) is below 20 or above
+ *     the datagram length becomes AIPSTACK_RX_DROP_TCP_OFFSET;
+ *   - d_segs[i]: for an accepted TCP frame with a valid offset the record above, opts / mss /
+ *     wnd_scale exactly what ParseTcpOptions leaves for the 4*offset - 20 option bytes (mss and
+ *     wnd_scale 0 where their flag is not set); 32 zero bytes for every other frame;
+ *   - d_pcb[i]: for a valid record the cookie of the table entry equal to {local_addr,
+ *     remote_addr, local_port, remote_port}, else AIPSTACK_TCP_NO_PCB.
+ * d_pcbs: n_pcbs entries in DEVICE memory, sorted by aipstack_tcp_pcb_table_sort, keys unique
+ * (n_pcbs == 0: no table, d_pcbs may be NULL). An unsorted table gives unspecified d_pcb values,
+ * never an access outside the table. Re-upload the table when a PCB is added or removed.
+ * Two stream-ordered passes: the Rx verify launch, unchanged, into d_verdict; then a parse
+ * pass, one frame per lane, that reads the verdict and (only of frames accepted as TCP) at
+ * most the first 134 header bytes, never past the frame's own length. Never allocates or
+ * synchronises; can be captured into a graph and repeated (outputs depend on inputs only).
+ * _EINVAL before any work for a null pointer, n or n_pcbs above 2^40, d_segs or d_pcbs not
+ * 8-byte aligned, d_pcb not 4-byte aligned, a slot stride outside
+ * (0, AIPSTACK_CHKSUM_MAX_SLOT_STRIDE]; n == 0 is a no-op. */
+int aipstack_tcp_rx_parse(const void *d_base, const uint64_t *d_offsets, uint64_t n,
+                          const aipstack_tcp_pcb_key *d_pcbs, uint64_t n_pcbs,
+                          uint8_t *d_verdict, aipstack_tcp_rx_seg *d_segs, uint32_t *d_pcb,
+                          void *stream);
+int aipstack_tcp_rx_parse_slotted(const void *d_base, uint64_t slot_stride, const uint32_t *d_len,
+                                  uint64_t n, const aipstack_tcp_pcb_key *d_pcbs, uint64_t n_pcbs,
+                                  uint8_t *d_verdict, aipstack_tcp_rx_seg *d_segs, uint32_t *d_pcb,
+                                  void *stream);
+
 /* ---- 3. host-memory streaming engine ----------------------------------------------- */
 
 /* The reference's packet path starts and ends in host memory (TAP read()/write(),
