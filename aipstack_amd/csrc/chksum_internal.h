@@ -39,6 +39,12 @@ int tuning_tx_header_mode(int family_default);
 constexpr int kTxStoreFields = 0, kTxStoreSectors = 1, kTxStoreLines = 2;
 int tuning_tx_store(int family_default);
 
+// Most blocks a one-element-per-lane pass launches (the header-split fill's, the burst
+// segmentation's and the Rx parse's passes, the split Tx fills' scatter): the tunable
+// "aux_blocks" when it is 1 or more (tests make a small batch run the grid-stride loops several
+// times), else 64 per compute unit.
+uint64_t tuning_aux_blocks(int cus);
+
 // Chains: chunks of at most this many bytes are read first in a group's gathered stream
 // (tunable "chain_short"; 0 = the table's order, -1 = the default, 128).
 int tuning_chain_short();

@@ -557,6 +557,8 @@ struct Tuning {
                                           // touched up front; else by kind of Tx launch
     std::atomic<int> tx_store{-1};        // in-place Tx fills: 0 = 2-byte field stores, 1 =
                                           // whole sectors; else the default
+    std::atomic<int> aux_blocks{-1};      // most blocks of a one-element-per-lane pass; below
+                                          // 1 = 64 per CU
     std::atomic<int> gather{1};           // back-to-back batches: -1 stream mode with 64-packet
                                           // chunks (rounds 1-3), 0 the gathered stream (round
                                           // 4), 1 (or 2) short runs (round 5, launch_short_runs)
@@ -1025,6 +1027,11 @@ int tuning_tx_store(int family_default) {
                                                                                 : family_default;
 }
 
+uint64_t tuning_aux_blocks(int cus) {
+    const int t = tuning().aux_blocks.load(std::memory_order_relaxed);
+    return t >= 1 ? (uint64_t)t : (uint64_t)cus * 64;
+}
+
 int tuning_frames_in_flight() {
     const int f = tuning().frames.load(std::memory_order_relaxed);
     return (f == 2 || f == 4 || f == 8) ? f : 4;
@@ -1168,6 +1175,7 @@ extern "C" int aipstack_chksum_tune(const char *key, int value) {
     else if (!std::strcmp(key, "chunk_packets")) t.chunk_packets = value;
     else if (!std::strcmp(key, "tx_gather")) t.tx_gather = value;
     else if (!std::strcmp(key, "tx_store")) t.tx_store = value;
+    else if (!std::strcmp(key, "aux_blocks")) t.aux_blocks = value;
     else if (!std::strcmp(key, "chain_short")) t.chain_short = value;
     else if (!std::strcmp(key, "gather")) t.gather = value;
     else if (!std::strcmp(key, "lds_pad")) t.lds_pad = value;

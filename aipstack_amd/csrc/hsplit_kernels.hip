@@ -292,7 +292,7 @@ extern "C" int aipstack_chksum_tx_fill_hsplit(void *d_hdr, uint64_t hdr_stride,
     uint32_t *seeds = static_cast<uint32_t *>(d_workspace);
     uint32_t *records = seeds + n;
     uint16_t *sums = reinterpret_cast<uint16_t *>(records + n);
-    const uint64_t want = (n + kHsBlock - 1) / kHsBlock, most = (uint64_t)cus * 64;
+    const uint64_t want = (n + kHsBlock - 1) / kHsBlock, most = tuning_aux_blocks(cus);
     const unsigned blocks = (unsigned)(want < most ? want : most);
     const uint64_t base = (uint64_t)(uintptr_t)d_hdr;
     hipLaunchKernelGGL(hsplit_header_kernel, dim3(blocks), dim3(kHsBlock), 0, s, base, hdr_stride,

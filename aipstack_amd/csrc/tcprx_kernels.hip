@@ -156,7 +156,7 @@ int launch_parse(const Frames &fr, uint64_t n, const aipstack_tcp_pcb_key *d_pcb
                  uint8_t *d_verdict, aipstack_tcp_rx_seg *d_segs, uint32_t *d_pcb, hipStream_t s) {
     const int cus = device_cu_count(s);
     if (cus <= 0) return AIPSTACK_CHKSUM_EHIP;
-    const uint64_t want = (n + kRxBlock - 1) / kRxBlock, most = (uint64_t)cus * 64;
+    const uint64_t want = (n + kRxBlock - 1) / kRxBlock, most = tuning_aux_blocks(cus);
     const unsigned blocks = (unsigned)(want < most ? want : most);
     const uint64_t segs = (uint64_t)(uintptr_t)d_segs;
     if ((segs & 15u) == 0u)

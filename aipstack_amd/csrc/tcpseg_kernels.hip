@@ -369,7 +369,7 @@ extern "C" int aipstack_tcp_tx_segment(const aipstack_tcp_burst *d_bursts,
     uint64_t *records = static_cast<uint64_t *>(d_workspace);
     uint32_t *seeds = reinterpret_cast<uint32_t *>(records + n);
     uint16_t *sums = reinterpret_cast<uint16_t *>(seeds + n);
-    const uint64_t want = (n + kTsBlock - 1) / kTsBlock, most = (uint64_t)cus * 64;
+    const uint64_t want = (n + kTsBlock - 1) / kTsBlock, most = tuning_aux_blocks(cus);
     const unsigned blocks = (unsigned)(want < most ? want : most);
     hipLaunchKernelGGL(tcpseg_plan_kernel, dim3(blocks), dim3(kTsBlock), 0, s, d_bursts,
                        d_seg_index, d_chunk_base, n_bursts, n, n_chunks, d_chunk_addr, d_chunk_len,

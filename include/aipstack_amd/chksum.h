@@ -700,7 +700,10 @@ int aipstack_chksum_device_check(int device);
  * 4); -1 = stream mode, one contiguous run per 64-packet chunk), "short_loads" (short runs: 0
  * stream prefixes, 1 the same through global loads, 2 column runs; -1 = by packet length, the
  * default), "lds_pad" (bytes of dynamic LDS per workgroup of the batch, chain and frame
- * kernels, which caps the workgroups per CU; -1 none, 0 the launch's own). Sweep builds only
+ * kernels, which caps the workgroups per CU; -1 none, 0 the launch's own), "aux_blocks" (most
+ * workgroups of a one-element-per-lane pass -- the header-split fill's two, the burst
+ * segmentation's plan and emit, the Rx parse, the split Tx fills' scatter: 1 or more; -1 = the
+ * default, 64 per CU; tests set 1 or 3 so that a small batch loops). Sweep builds only
  * (tools/build_variant.sh NAME -DAIPSTACK_ALL_VARIANTS; the product build rejects values other
  * than the default): "unroll" (segments per lane issued up front, 1..4), "packets" (packets a
  * wave keeps in flight: 1, 2, 4, 8), "nontemporal" (0/1), "frames" (frames in flight per wave

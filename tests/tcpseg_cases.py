@@ -404,3 +404,35 @@ def mismatch_batch():
           burst((1, 1500), give=(3, 6), **three), good(4),
           burst((1, 1500), give=(0, 2), **three), good(5)]
     return Batch(cs, pay)
+
+
+def multipass_batch(n):
+    """Exactly n segments from the ingredients of boundary_batch (three bursts and more per
+    wave), invalid_batch (bursts that break the contract), three bursts of 100 segments (waves
+    of two bursts) and sizes_batch (one burst of 200 segments: waves of one burst), in that
+    order, each burst taken if it still fits; one-segment bursts make up the rest."""
+    pay = payload_bytes()
+    cs, total = [], 0
+    hundred = [burst((3 + j, 100 * 97 - j), mss=97, seq=0xFFFFF000, ip_id=0xFFC0 + j) for j in range(3)]
+    for c in boundary_batch().cases + invalid_batch().cases + hundred + sizes_batch().cases:
+        ns = c["give"][0] if "give" in c else len(segments_of(c))
+        if total + ns <= n:
+            cs.append(c)
+            total += ns
+    cs += one_segment_bursts(n - total).cases
+    return Batch(cs, pay)
+
+
+def burst_loop_batch(n_bad=700):
+    """One valid one-segment burst, then `n_bad` bursts that break the contract while owning
+    chunk entries but no segment: invalid_case of every class (3 entries each) in turn with
+    valid descriptors whose index gives them no segment and 2 entries."""
+    cs = [burst((5, 700), mss=1460, ip_id=77)]
+    for j in range(n_bad):
+        if j & 1:
+            cs.append(burst((10 * j + 1, 1500), mss=500, ip_id=j, give=(0, 2)))
+        else:
+            c = invalid_case(INVALID_CLASSES[(j // 2) % len(INVALID_CLASSES)])
+            c["give"] = (0, 3)
+            cs.append(c)
+    return Batch(cs, payload_bytes())

@@ -273,7 +273,106 @@ def test_prefilled_fields_are_taken_as_zero(oracle):
     assert ((want_st == H.ACCEPT) & ok).sum() >= 500
 
 
-# ---- 6. diagnostics (last: after all of the above) ---------------------------------------
+# ---- 6. later iterations of the grid-stride loops ----------------------------------------
+
+GUARD, GUARD_BYTE, POISON = 256, 0xA7, 0xC3
+_ring_cache = {}
+
+
+def _ring_case(oracle, n, stride):
+    """ring_batch(n) at `stride` and what the oracle makes of its linear frames (computed once,
+    shared, never modified)."""
+    if (n, stride) not in _ring_cache:
+        slots, lens, payload, linear = H.ring_batch(n, seed=700 + n, stride=stride)
+        flat = linear.reshape(-1).copy()
+        off = np.arange(n + 1, dtype=np.uint64) * np.uint64(linear.shape[1])
+        st = oracle.tx_fill_batch(flat, off)
+        want = slots.reshape(n, -1).copy()
+        want[:, :54] = flat.reshape(n, -1)[:, :54]
+        assert np.array_equal(flat.reshape(n, -1)[:, 54:], linear[:, 54:]) and (st == H.ACCEPT).all()
+        for a in (slots, lens, payload, want, st):
+            a.setflags(write=False)
+        _ring_cache[n, stride] = (slots, lens, payload, want.reshape(-1), st)
+    return _ring_cache[n, stride]
+
+
+def _ring_fill(case, stride, cap):
+    """The fill at block cap `cap` on fresh copies, statuses poisoned, guards round the ring and
+    the statuses: (statuses, ring) as the GPU left them."""
+    slots, lens, payload, _, _ = case
+    n = lens.size
+    ring = torch.full((GUARD + n * stride + GUARD,), GUARD_BYTE, dtype=torch.uint8, device=DEV)
+    ring[GUARD:GUARD + n * stride] = _d(slots.copy())
+    status = torch.full((GUARD + n + GUARD,), GUARD_BYTE, dtype=torch.uint8, device=DEV)
+    status[GUARD:GUARD + n] = POISON
+    dp = _d(payload.copy())
+    addr = _d(dp.data_ptr() + 1460 * np.arange(n, dtype=np.int64))
+    _tune("aux_blocks", cap)
+    try:
+        A.tx_fill_header_split(ring[GUARD:GUARD + n * stride], stride, _d(lens.view(np.int32).copy()),
+                               addr, _d(np.full(n, 1460, dtype=np.int32)),
+                               _d(np.arange(n + 1, dtype=np.int64)), out=status[GUARD:GUARD + n])
+        torch.cuda.synchronize()
+    finally:
+        _tune("aux_blocks", -1)
+    assert np.array_equal(dp.cpu().numpy(), payload)
+    hs, hr = status.cpu().numpy(), ring.cpu().numpy()
+    for h, m in ((hs, n), (hr, n * stride)):
+        assert (h[:GUARD] == GUARD_BYTE).all() and (h[GUARD + m:] == GUARD_BYTE).all()
+    return hs[GUARD:GUARD + n], hr[GUARD:GUARD + n * stride]
+
+
+@pytest.mark.parametrize("stride", [64, 72])
+@pytest.mark.parametrize("cap", [1, 3])
+@pytest.mark.parametrize("n", [257, 1000, 1537])
+def test_later_iterations_of_both_passes(oracle, n, cap, stride):
+    """At most `cap` blocks ("aux_blocks"): the header and the finish pass loop (1000 segments at
+    cap 1: four iterations, the last with a partial wave; 1537 at cap 3: a third iteration in
+    which only block 0 has work). Every segment from 256 * cap on is produced by a later
+    iteration alone."""
+    case = _ring_case(oracle, n, stride)
+    st, ring = _ring_fill(case, stride, cap)
+    bad = np.nonzero(st != case[4])[0]
+    assert bad.size == 0, (bad[:8], st[bad[:8]])
+    rows = np.nonzero((ring != case[3]).reshape(n, stride).any(axis=1))[0]
+    assert rows.size == 0, rows[:8]
+    st0, ring0 = _ring_fill(case, stride, -1)
+    assert np.array_equal(st, st0) and np.array_equal(ring, ring0)
+
+
+def test_later_iterations_on_a_mixed_layout(oracle):
+    """Every status class, odd in-slot lengths and three chunks per segment at one block."""
+    _tune("aux_blocks", 1)
+    try:
+        _check(oracle, _mixed_layout())
+    finally:
+        _tune("aux_blocks", -1)
+
+
+def test_later_iterations_of_the_split_fill_scatter(oracle):
+    """tx_fill(split=True) and tx_fill_slotted(split=True) on 1000 frames with the scatter pass
+    at one block, against the frame oracle."""
+    from aipstack_amd import synth
+    fr, off = synth.frames_host(1000, seed=4321, max_payload=600)
+    want = fr.copy()
+    want_st = oracle.tx_fill_batch(want, off)
+    ring, lens = synth.to_slots(fr, off, 2048, slack_seed=9)
+    want_ring = ring.copy()
+    want_rst = oracle.tx_fill_slotted(want_ring, 2048, lens)
+    assert set(want_st[256:].tolist()) == {0, 3, 6, 8} and np.array_equal(want_st, want_rst)
+    _tune("aux_blocks", 1)
+    try:
+        d = _d(fr)
+        st = A.tx_fill(d, _d(off), split=True).cpu().numpy()
+        dr = _d(ring)
+        rst = A.tx_fill_slotted(dr, 2048, _d(lens.view(np.int32)), split=True).cpu().numpy()
+    finally:
+        _tune("aux_blocks", -1)
+    assert np.array_equal(st, want_st) and np.array_equal(d.cpu().numpy(), want)
+    assert np.array_equal(rst, want_rst) and np.array_equal(dr.cpu().numpy(), want_ring)
+
+
+# ---- 7. diagnostics (last: after all of the above) ---------------------------------------
 
 def test_no_contract_violations():
     assert A.contract_violations() == 0

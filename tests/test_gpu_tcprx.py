@@ -314,6 +314,68 @@ def test_slotted_equals_csr(oracle, stride):
     A.contract_violations(clear=True)        # the lengths above the stride were reported
 
 
+# ---- later iterations of the grid-stride loop --------------------------------------------------
+
+def _tune(key, value):
+    from aipstack_amd import _lib
+    assert _lib.load().aipstack_chksum_tune(key.encode(), value) == A.AIPSTACK_CHKSUM_OK
+
+
+def _multipass_set(oracle, n):
+    """n frames: mixed_frames (every verdict class) with the bad_offsets set from frame 800 on
+    (or at the end of a short batch); their verdicts, a table, the expectation. Computed once."""
+    name = f"multipass{n}"
+    if name not in _cache:
+        b, bv = _set(oracle, "bad_offsets")
+        m = T.mixed_frames(n - len(b))
+        buf, off = F.pack(m)
+        mv = oracle.rx_verify_batch(buf, off)
+        at = 800 if len(m) > 800 else len(m)
+        frames, v = m[:at] + b + m[at:], np.concatenate([mv[:at], bv, mv[at:]])
+        tbl = _table_for(frames, v, every=2)
+        _cache[name] = (frames, v, tbl, T.expected(frames, v, tbl, A.TCP_RX_SEG_DTYPE))
+    return _cache[name]
+
+
+@pytest.mark.parametrize("seg_shift", [0, 8])
+@pytest.mark.parametrize("cap", [1, 3])
+@pytest.mark.parametrize("n", [257, 1000, 1537])
+def test_later_iterations_of_the_parse(oracle, n, cap, seg_shift):
+    """At most `cap` blocks ("aux_blocks"): the parse loops, in both store forms (seg_shift 0:
+    records through LDS; 8: per-lane stores), over CSR frames and over ring slots; every record
+    from 256 * cap on is produced by a later iteration alone, on poisoned memory."""
+    frames, v, tbl, e = _multipass_set(oracle, n)
+    assert len(frames) == n
+    late = slice(256 * cap, None)
+    if n >= 1000:
+        assert (e.verdict[late] == T.DROP_TCP_OFFSET).sum() == 30
+        assert (e.pcb[late] != T.NO_PCB).any() and (e.segs["opts"][late] == 0).any()
+    buf, off = F.pack(frames)
+    dbuf, doff = torch.from_numpy(buf).to(DEV), torch.from_numpy(off.view(np.int64)).to(DEV)
+    stride = 2048
+    ring = np.full(n * stride, 0x3C, dtype=np.uint8)
+    lens = np.array([len(f) for f in frames], dtype=np.uint32)
+    assert int(lens.max()) <= stride
+    for i, f in enumerate(frames):
+        ring[i * stride:i * stride + len(f)] = np.frombuffer(f, dtype=np.uint8)
+    dring, dlens = torch.from_numpy(ring).to(DEV), torch.from_numpy(lens.view(np.int32)).to(DEV)
+    got = {}
+    for c in (cap, -1):
+        _tune("aux_blocks", c)
+        try:
+            out = Outputs(n, seg_shift)
+            A.tcp_rx_parse(dbuf, doff, tbl, **out.kw())
+            _compare(e, out)
+            slot = Outputs(n, seg_shift)
+            A.tcp_rx_parse_slotted(dring, stride, dlens, tbl, **slot.kw())
+            _compare(e, slot)
+        finally:
+            _tune("aux_blocks", -1)
+        got[c] = (out.bytes(), slot.bytes())
+    assert got[cap] == got[-1] and got[cap][0] == got[cap][1]
+    assert A.contract_violations(clear=True) == 0
+
+
 # ---- closing the loop with the send side -------------------------------------------------------
 
 def test_segments_of_tcp_tx_segment_parse_back(oracle):

@@ -277,7 +277,76 @@ def test_captured_in_a_graph_on_a_side_stream(oracle):
         _compare(e, out, 64, dpay, batch.payload)
 
 
-# ---- 6. diagnostics (last: after all of the above) ---------------------------------------
+# ---- 6. later iterations of the grid-stride loops ----------------------------------------
+
+def _tune(key, value):
+    from aipstack_amd import _lib
+    assert _lib.load().aipstack_chksum_tune(key.encode(), value) == A.AIPSTACK_CHKSUM_OK
+
+
+for _n in (257, 1000, 1537):
+    _BATCHES[f"multipass{_n}"] = lambda o, n=_n: T.multipass_batch(n)
+_BATCHES["burst_loop"] = lambda o: T.burst_loop_batch()
+
+
+def _wave_kinds(e, first):
+    """What the waves from segment `first` on hold: {"one", "two", "more"} bursts, "invalid"."""
+    kinds = set()
+    for w in range(first, len(e.status), 64):
+        nb = len(set(e.seg_case[w:w + 64].tolist()))
+        kinds.add("one" if nb == 1 else "two" if nb == 2 else "more")
+        if (e.status[w:w + 64] == T.BURST_INVALID).any():
+            kinds.add("invalid")
+    return kinds
+
+
+def _all_bytes(out):
+    return [t.cpu().numpy().tobytes() for t in (out.seg.headers, out.seg.chunk_addr,
+                                                out.seg.chunk_len, out.seg.chunk_index, out.seg.status)]
+
+
+@pytest.mark.parametrize("stride,shift", [(64, 0), (72, 3)])
+@pytest.mark.parametrize("cap", [1, 3])
+@pytest.mark.parametrize("n", [257, 1000, 1537])
+def test_later_iterations_of_plan_and_emit(oracle, n, cap, stride, shift):
+    """At most `cap` blocks ("aux_blocks"): the plan pass and both emit forms loop; every segment
+    from 256 * cap on is produced by a later iteration alone, on poisoned memory."""
+    name = f"multipass{n}"
+    _, si, _, e = _case(oracle, name)
+    assert int(si[-1]) == n
+    if n == 1537:
+        assert _wave_kinds(e, 256) == {"one", "two", "more", "invalid"}
+        assert T.count_straddle_odd_first(e) >= 1
+    _tune("aux_blocks", cap)
+    try:
+        batch, si, cb, e, desc, dpay, out = _run(oracle, name, stride=stride, shift=shift)
+        torch.cuda.synchronize()
+    finally:
+        _tune("aux_blocks", -1)
+    assert (out.seg.headers.data_ptr() % 64 == 0) == (shift == 0)
+    capped = _all_bytes(out)
+    out.reset()
+    A.tcp_tx_segment(desc, si, cb, out=out.seg)
+    _compare(e, out, stride, dpay, batch.payload)
+    assert _all_bytes(out) == capped
+
+
+def test_burst_loop_runs_past_the_grid(oracle):
+    """One segment, so one block of 256 lanes, and 700 bursts that break the contract while
+    owning chunk entries: bursts 256 to 700 are emptied by later iterations of the burst loop."""
+    batch, si, cb, e, _, _, out = _run(oracle, "burst_loop")
+    assert int(si[-1]) == 1 and len(batch.cases) == 701 and e.status[0] == T.ACCEPT
+    first = int(cb[256])
+    assert int(cb[-1]) - first == 223 * 2 + 222 * 3 and (e.chunk_off[first:] == -1).all()
+    assert not out.seg.chunk_addr.cpu().numpy()[first:].any()
+    assert not out.seg.chunk_len.cpu().numpy()[first:].any()
+    idx = out.seg.chunk_index.cpu().numpy().view(np.uint64)
+    assert (np.diff(idx.astype(np.int64)) >= 0).all() and idx[0] == 0 and idx[1] == cb[-1]
+    assert e.chunk_off[0] == 5 and e.chunk_len[0] == 700          # the one valid entry
+    _run(oracle, "burst_loop", stride=72, shift=5)
+
+
+# ---- 7. diagnostics (last: after all of the above) ---------------------------------------
 
 def test_no_contract_violations():
     assert A.contract_violations() == 0
