@@ -1110,20 +1110,34 @@ def tx_fill(frames, offsets, *, out=None, stream=None, split=None, workspace=Non
     return out
 
 
+def _launch_stream(stream, dev):
+    """`stream` as a torch stream of device `dev` (record_stream wants one): torch's current
+    stream for None, an ExternalStream for a raw hipStream_t handle."""
+    torch = _torch()
+    launch_stream = torch.cuda.current_stream(dev) if stream is None else stream
+    if not hasattr(launch_stream, "cuda_stream"):  # a raw hipStream_t handle
+        launch_stream = torch.cuda.ExternalStream(int(launch_stream), device=dev)
+    return launch_stream
+
+
+def _workspace(workspace, need: int, like, like_name: str):
+    """(workspace, its size in bytes): the caller's tensor, which must be on `like`'s device (the
+    library checks its size and alignment), or `need` bytes from torch's allocator."""
+    if workspace is None:
+        torch = _torch()
+        workspace = torch.empty(need, dtype=torch.uint8, device=like.device)
+    else:
+        _require_device(workspace, "workspace")
+        _same_device(like, workspace, f"{like_name} and workspace")
+    return workspace, workspace.numel() * workspace.element_size()
+
+
 def _split_call(lib, name, frames, n, stream, workspace, args):
     """A split Tx fill (read pass + scatter pass through a workspace of 8 bytes per frame):
     ``args(workspace_ptr, workspace_bytes, stream_handle)`` gives the entry point's arguments."""
-    torch = _torch()
     need = int(lib.aipstack_chksum_tx_fill_workspace_bytes(max(n, 0)))
-    if workspace is None:
-        workspace = torch.empty(max(need, 8), dtype=torch.uint8, device=frames.device)
-    else:
-        _require_device(workspace, "workspace")
-        _same_device(frames, workspace, "frames and workspace")
-    ws_bytes = workspace.numel() * workspace.element_size()
-    launch_stream = torch.cuda.current_stream(frames.device) if stream is None else stream
-    if not hasattr(launch_stream, "cuda_stream"):  # a raw hipStream_t handle
-        launch_stream = torch.cuda.ExternalStream(int(launch_stream), device=frames.device)
+    workspace, ws_bytes = _workspace(workspace, max(need, 8), frames, "frames")
+    launch_stream = _launch_stream(stream, frames.device)
     _check(getattr(lib, name)(*args(workspace.data_ptr(), ws_bytes,
                                     _stream_handle(launch_stream))), name)
     # The caching allocator must not hand the workspace out again before both passes on
@@ -1176,15 +1190,8 @@ def tx_fill_header_split(headers, hdr_stride: int, hdr_lens, chunk_addr, chunk_l
         chunk_len = torch.zeros(1, dtype=torch.int32, device=headers.device)
     lib = _lib.load()
     need = int(lib.aipstack_chksum_tx_fill_hsplit_workspace_bytes(n))
-    if workspace is None:
-        workspace = torch.empty(need, dtype=torch.uint8, device=headers.device)
-    else:
-        _require_device(workspace, "workspace")
-        _same_device(headers, workspace, "headers and workspace")
-    ws_bytes = workspace.numel() * workspace.element_size()
-    launch_stream = torch.cuda.current_stream(headers.device) if stream is None else stream
-    if not hasattr(launch_stream, "cuda_stream"):  # a raw hipStream_t handle
-        launch_stream = torch.cuda.ExternalStream(int(launch_stream), device=headers.device)
+    workspace, ws_bytes = _workspace(workspace, need, headers, "headers")
+    launch_stream = _launch_stream(stream, headers.device)
     _check(lib.aipstack_chksum_tx_fill_hsplit(
         headers.data_ptr(), hdr_stride, hdr_lens.data_ptr(), chunk_addr.data_ptr(),
         chunk_len.data_ptr(), chunk_index.data_ptr(), n, out.data_ptr(), workspace.data_ptr(),
@@ -1225,14 +1232,6 @@ def tcp_burst_layout(bursts):
                                                  seg_index.ctypes.data, chunk_base.ctypes.data),
            "aipstack_tcp_burst_layout")
     return seg_index, chunk_base
-
-
-def _launch_stream(stream, dev):
-    torch = _torch()
-    launch_stream = torch.cuda.current_stream(dev) if stream is None else stream
-    if not hasattr(launch_stream, "cuda_stream"):  # a raw hipStream_t handle
-        launch_stream = torch.cuda.ExternalStream(int(launch_stream), device=dev)
-    return launch_stream
 
 
 class TcpSegments:
@@ -1349,12 +1348,7 @@ def tcp_tx_segment(bursts, seg_index, chunk_base, *, hdr_stride: int = 64, heade
         return res
     lib = _lib.load()
     need = int(lib.aipstack_tcp_tx_segment_workspace_bytes(n))
-    if workspace is None:
-        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
-    else:
-        _require_device(workspace, "workspace")
-        _same_device(headers, workspace, "headers and workspace")
-    ws_bytes = workspace.numel() * workspace.element_size()
+    workspace, ws_bytes = _workspace(workspace, need, headers, "headers")
     launch_stream = _launch_stream(stream, dev)
     # no chunk at all (FIN-only bursts): the C-ABI wants non-null tables (storage of 1 entry)
     ca, cl = res.chunk_addr, res.chunk_len

@@ -12,15 +12,12 @@
 
 #include "aipstack_amd/chksum.h"
 #include "chksum_internal.h"
+#include "lane_pass.h"
 
 namespace aipstack_amd {
 namespace {
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int kWave = 64;
-constexpr int kWavesPerBlock = 4;
-constexpr int kBlock = kWave * kWavesPerBlock;
+constexpr int kWavesPerBlock = kBlock / kWave;
 
 // Contract violations seen by this translation unit's kernels on this device: sticky bits
 // (AIPSTACK_CHKSUM_VIOLATION_*, chksum.h), read and cleared from the host through
@@ -1728,16 +1725,6 @@ __device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
     v += __builtin_amdgcn_update_dpp(0u, v, 0x142, 0xA, 0xF, false);
     v += __builtin_amdgcn_update_dpp(0u, v, 0x143, 0xC, 0xF, false);
     return __builtin_amdgcn_readlane(v, 63);
-}
-
-__device__ __forceinline__ uint32_t fold16(uint32_t s) {
-    s = (s & 0xFFFFu) + (s >> 16);
-    s = (s & 0xFFFFu) + (s >> 16);
-    return s;
-}
-
-__device__ __forceinline__ uint32_t bswap16(uint32_t x) {
-    return ((x & 0xFFu) << 8) | ((x >> 8) & 0xFFu);
 }
 
 }  // namespace

@@ -1064,9 +1064,8 @@ int launch_frames(const void *d_base, const uint64_t *d_offsets, uint64_t n, uin
     }
     if (st != AIPSTACK_CHKSUM_OK) return st;
     if (SPLIT && scatter) {
-        const uint64_t sblocks = min((n + kBlock - 1) / kBlock, tuning_aux_blocks(cus));
-        hipLaunchKernelGGL(tx_scatter_kernel, dim3((unsigned)sblocks), dim3(kBlock), 0, stream,
-                           desc.base, d_offsets, d_records, d_status, n);
+        hipLaunchKernelGGL(tx_scatter_kernel, dim3(lane_pass_blocks(n, cus)), dim3(kBlock), 0,
+                           stream, desc.base, d_offsets, d_records, d_status, n);
         return check_hip(hipGetLastError());
     }
     return AIPSTACK_CHKSUM_OK;
@@ -1118,9 +1117,8 @@ int launch_frames_slotted(const void *d_base, uint64_t slot_stride, const uint32
     if (st != AIPSTACK_CHKSUM_OK || !SPLIT || !d_status) return st;
     // the split slotted fill's scatter pass (records pass above: d_status is null for the
     // records-only call)
-    const uint64_t sblocks = min((n + kBlock - 1) / kBlock, tuning_aux_blocks(cus));
-    hipLaunchKernelGGL(tx_scatter_slotted_kernel, dim3((unsigned)sblocks), dim3(kBlock), 0, stream,
-                       desc.base, slot_stride, d_records, d_status, n);
+    hipLaunchKernelGGL(tx_scatter_slotted_kernel, dim3(lane_pass_blocks(n, cus)), dim3(kBlock), 0,
+                       stream, desc.base, slot_stride, d_records, d_status, n);
     return check_hip(hipGetLastError());
 }
 

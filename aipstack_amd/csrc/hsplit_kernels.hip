@@ -27,11 +27,11 @@
 
 #include "aipstack_amd/chksum.h"
 #include "chksum_internal.h"
+#include "lane_pass.h"
 
 namespace aipstack_amd {
 namespace {
 
-constexpr int kHsBlock = 256;
 constexpr uint32_t kMaxSplitHeader = AIPSTACK_CHKSUM_MAX_SPLIT_HEADER;
 
 // The record of segment i (workspace, 4 bytes): bits 0-15 the IPv4 header checksum, 16-23 the
@@ -39,27 +39,6 @@ constexpr uint32_t kMaxSplitHeader = AIPSTACK_CHKSUM_MAX_SPLIT_HEADER;
 // 24), 25 = write the L4 field, 26 = UDP (0 is sent as 0xFFFF), 27 = the chain sum comes back
 // byte-swapped (odd split), 28-31 the status.
 constexpr uint32_t kRecIp = 1u << 24, kRecL4 = 1u << 25, kRecUdp = 1u << 26, kRecSwap = 1u << 27;
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-// Slot accesses go through global (address space 1) pointers made from the slot's address, so
-// that they are global_load / global_store instructions, at any byte alignment (gfx9 under ROCm
-// runs in unaligned-access mode: one instruction each).
-#define AIPSTACK_HS_GLOBAL __attribute__((address_space(1)))
-typedef AIPSTACK_HS_GLOBAL const u32x4 g_seg;
-typedef AIPSTACK_HS_GLOBAL const uint16_t g_u16_any __attribute__((aligned(1)));
-typedef AIPSTACK_HS_GLOBAL const uint32_t g_u32_any __attribute__((aligned(1)));
-typedef AIPSTACK_HS_GLOBAL const u32x4 g_seg_any __attribute__((aligned(1)));
-typedef AIPSTACK_HS_GLOBAL uint16_t g_field __attribute__((aligned(1)));
-
-__device__ __forceinline__ uint32_t hs_bswap16(uint32_t x) {
-    return ((x & 0xFFu) << 8) | ((x >> 8) & 0xFFu);
-}
-
-// x mod 0xFFFF with a nonzero multiple as 0xFFFF: zero only for x = 0.
-__device__ __forceinline__ uint32_t hs_fold16(uint32_t x) {
-    x = (x & 0xFFFFu) + (x >> 16);
-    return (x & 0xFFFFu) + (x >> 16);
-}
 
 // Mask of the bytes [lo, hi) of a dword (byte 0 = bits 0-7), clipped to the dword.
 __device__ __forceinline__ uint32_t hs_keep(int lo, int hi) {
@@ -71,15 +50,15 @@ __device__ __forceinline__ uint32_t hs_keep(int lo, int hi) {
 }
 
 __device__ __forceinline__ uint32_t hs_be16(uint32_t le_dword, int byte) {  // byte 0 or 2
-    return hs_bswap16(le_dword >> (8 * byte));
+    return bswap16(le_dword >> (8 * byte));
 }
 
 // Sum of a big-endian byte sequence from a halves-sum (little-endian 16-bit halves at even
 // ABSOLUTE addresses) of its bytes: the halves are the byte-swapped words when the sequence
 // starts at an even address, the words themselves when it starts at an odd one.
 __device__ __forceinline__ uint32_t hs_orient(uint32_t halves_sum, uint32_t start_abs) {
-    const uint32_t f = hs_fold16(halves_sum);
-    return (start_abs & 1u) ? f : hs_bswap16(f);
+    const uint32_t f = fold16(halves_sum);
+    return (start_abs & 1u) ? f : bswap16(f);
 }
 
 // The two sums of one aligned 16-byte segment whose byte 0 is slot byte `pos` (may be
@@ -102,13 +81,13 @@ __device__ __forceinline__ void hs_add_segment(const u32x4 &v, int pos, int ip_e
 // Header pass. The staged layout rule (chksum.h): every byte the linear fill would parse or
 // write lies in the slot, else AIPSTACK_TX_SPLIT_LAYOUT; the verdicts of the linear fill that
 // need fewer bytes than a stage asks for come first, as it gives them.
-__global__ __launch_bounds__(kHsBlock) void hsplit_header_kernel(
+__global__ __launch_bounds__(kBlock) void hsplit_header_kernel(
     uint64_t hdr_base, uint64_t hdr_stride, const uint32_t *__restrict__ hdr_len,
     const uint32_t *__restrict__ chunk_len, const uint64_t *__restrict__ chunk_index, uint64_t n,
     uint32_t *__restrict__ seeds, uint32_t *__restrict__ records) {
-    const uint64_t step = (uint64_t)gridDim.x * kHsBlock;
+    const uint64_t step = (uint64_t)gridDim.x * kBlock;
     const uint32_t cap = (uint32_t)(hdr_stride < kMaxSplitHeader ? hdr_stride : kMaxSplitHeader);
-    for (uint64_t i = (uint64_t)blockIdx.x * kHsBlock + threadIdx.x; i < n; i += step) {
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += step) {
         const uint64_t P = hdr_base + i * hdr_stride;
         const uint32_t H = hdr_len[i];
         // payload bytes: the segment's chunk lengths (usually one or two)
@@ -125,17 +104,17 @@ __global__ __launch_bounds__(kHsBlock) void hsplit_header_kernel(
             u32x4 pre[4];
 #pragma unroll
             for (int k = 0; k < 4; ++k)
-                pre[k] = (uint32_t)k < nseg ? reinterpret_cast<g_seg *>(A0)[k]
+                pre[k] = (uint32_t)k < nseg ? reinterpret_cast<global_t<const u32x4> *>(A0)[k]
                                             : u32x4{0u, 0u, 0u, 0u};
             // the fixed fields, from the slot at any alignment (the bytes are in the slot:
             // H >= 14 for the EtherType, H >= 34 for the IPv4 header's first 20 bytes)
             const uint32_t ethertype =
-                H >= 14u ? hs_bswap16(*reinterpret_cast<g_u16_any *>(P + 12)) : 0u;
+                H >= 14u ? bswap16(*reinterpret_cast<global_t<const uint16_t, 1> *>(P + 12)) : 0u;
             u32x4 ip = {0u, 0u, 0u, 0u};
             uint32_t ip4 = 0;
             if (H >= 34u) {
-                ip = *reinterpret_cast<g_seg_any *>(P + 14);
-                ip4 = *reinterpret_cast<g_u32_any *>(P + 30);
+                ip = *reinterpret_cast<global_t<const u32x4, 1> *>(P + 14);
+                ip4 = *reinterpret_cast<global_t<const uint32_t, 1> *>(P + 30);
             }
             const uint32_t vihl = ip[0] & 0xFFu;
             const int hl = vihl == 0x45u ? 20 : (int)(vihl & 0xFu) * 4;
@@ -187,8 +166,8 @@ __global__ __launch_bounds__(kHsBlock) void hsplit_header_kernel(
                     if (H < (uint32_t)(dg + fixed)) {
                         layout_ok = false;
                     } else if (udp) {
-                        const int ulen = (int)hs_bswap16(
-                            *reinterpret_cast<g_u16_any *>(P + (uint64_t)dg + 4));
+                        const int ulen = (int)bswap16(
+                            *reinterpret_cast<global_t<const uint16_t, 1> *>(P + (uint64_t)dg + 4));
                         if (ulen < 8 || ulen > dlen) {
                             status = AIPSTACK_RX_DROP_L4_MALFORMED;
                             fixed = 0;
@@ -212,7 +191,7 @@ __global__ __launch_bounds__(kHsBlock) void hsplit_header_kernel(
                     for (int k = 0; k < 4; ++k)
                         hs_add_segment(pre[k], 16 * k - (int)rs, dg, dg, l4_end, fld, ip_sum, l4_sum);
                     for (uint32_t k = 4; k < nseg; ++k) {
-                        const u32x4 v = reinterpret_cast<g_seg *>(A0)[k];
+                        const u32x4 v = reinterpret_cast<global_t<const u32x4> *>(A0)[k];
                         hs_add_segment(v, 16 * (int)k - (int)rs, dg, dg, l4_end, fld, ip_sum, l4_sum);
                     }
                     const uint32_t hchk = ~hs_orient(ip_sum, rs + 14u) & 0xFFFFu;
@@ -221,7 +200,7 @@ __global__ __launch_bounds__(kHsBlock) void hsplit_header_kernel(
                         seed = words + hs_orient(l4_sum, rs + (uint32_t)dg);
                         rec |= (uint32_t)fld << 16 | kRecL4 | (udp ? kRecUdp : 0u);
                         if ((H - (uint32_t)dg) & 1u) {
-                            seed = hs_bswap16(hs_fold16(seed));
+                            seed = bswap16(fold16(seed));
                             rec |= kRecSwap;
                         }
                     }
@@ -235,24 +214,24 @@ __global__ __launch_bounds__(kHsBlock) void hsplit_header_kernel(
 
 // Finish pass: the chain kernel's sums (seed (+) payload, not inverted) become the field
 // values; fields and statuses stored. Rejected segments' sums are discarded.
-__global__ __launch_bounds__(kHsBlock) void hsplit_finish_kernel(
+__global__ __launch_bounds__(kBlock) void hsplit_finish_kernel(
     uint64_t hdr_base, uint64_t hdr_stride, const uint32_t *__restrict__ records,
     const uint16_t *__restrict__ sums, uint8_t *__restrict__ status, uint64_t n) {
-    const uint64_t step = (uint64_t)gridDim.x * kHsBlock;
-    for (uint64_t i = (uint64_t)blockIdx.x * kHsBlock + threadIdx.x; i < n; i += step) {
+    const uint64_t step = (uint64_t)gridDim.x * kBlock;
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += step) {
         const uint32_t rec = __builtin_nontemporal_load(&records[i]);
         const uint64_t P = hdr_base + i * hdr_stride;
         status[i] = (uint8_t)(rec >> 28);
         if (rec & kRecIp)
-            __builtin_nontemporal_store((uint16_t)hs_bswap16(rec & 0xFFFFu),
-                                        reinterpret_cast<g_field *>(P + 24));
+            __builtin_nontemporal_store((uint16_t)bswap16(rec & 0xFFFFu),
+                                        reinterpret_cast<global_t<uint16_t, 1> *>(P + 24));
         if (rec & kRecL4) {
             uint32_t r = __builtin_nontemporal_load(&sums[i]);
-            if (rec & kRecSwap) r = hs_bswap16(r);
+            if (rec & kRecSwap) r = bswap16(r);
             uint32_t chk = ~r & 0xFFFFu;
             if ((rec & kRecUdp) && chk == 0) chk = 0xFFFFu;  // udp/IpUdpProto.h:176-178
-            __builtin_nontemporal_store((uint16_t)hs_bswap16(chk),
-                                        reinterpret_cast<g_field *>(P + ((rec >> 16) & 0xFFu)));
+            __builtin_nontemporal_store((uint16_t)bswap16(chk),
+                                        reinterpret_cast<global_t<uint16_t, 1> *>(P + ((rec >> 16) & 0xFFu)));
         }
     }
 }
@@ -287,22 +266,21 @@ extern "C" int aipstack_chksum_tx_fill_hsplit(void *d_hdr, uint64_t hdr_stride,
         ((uintptr_t)d_workspace & 7u) != 0)
         return AIPSTACK_CHKSUM_EINVAL;
     const hipStream_t s = (hipStream_t)stream;
-    const int cus = device_cu_count(s);
-    if (cus <= 0) return AIPSTACK_CHKSUM_EHIP;
+    unsigned blocks;
+    int st = lane_pass_blocks(n, s, &blocks);
+    if (st != AIPSTACK_CHKSUM_OK) return st;
     uint32_t *seeds = static_cast<uint32_t *>(d_workspace);
     uint32_t *records = seeds + n;
     uint16_t *sums = reinterpret_cast<uint16_t *>(records + n);
-    const uint64_t want = (n + kHsBlock - 1) / kHsBlock, most = tuning_aux_blocks(cus);
-    const unsigned blocks = (unsigned)(want < most ? want : most);
     const uint64_t base = (uint64_t)(uintptr_t)d_hdr;
-    hipLaunchKernelGGL(hsplit_header_kernel, dim3(blocks), dim3(kHsBlock), 0, s, base, hdr_stride,
+    hipLaunchKernelGGL(hsplit_header_kernel, dim3(blocks), dim3(kBlock), 0, s, base, hdr_stride,
                        d_hdr_len, d_chunk_len, d_chunk_index, n, seeds, records);
-    int st = check_hip(hipGetLastError());
+    st = check_hip(hipGetLastError());
     if (st != AIPSTACK_CHKSUM_OK) return st;
     st = aipstack_chksum_batch_chain(d_chunk_addr, d_chunk_len, d_chunk_index, seeds, n, sums,
                                      flags & AIPSTACK_CHKSUM_JUST_WRITTEN, stream);
     if (st != AIPSTACK_CHKSUM_OK) return st;
-    hipLaunchKernelGGL(hsplit_finish_kernel, dim3(blocks), dim3(kHsBlock), 0, s, base, hdr_stride,
+    hipLaunchKernelGGL(hsplit_finish_kernel, dim3(blocks), dim3(kBlock), 0, s, base, hdr_stride,
                        records, sums, d_status, n);
     return check_hip(hipGetLastError());
 }

@@ -19,26 +19,11 @@
 
 #include "aipstack_amd/chksum.h"
 #include "chksum_internal.h"
+#include "lane_pass.h"
 #include "tcprx_common.h"
 
 namespace aipstack_amd {
 namespace {
-
-constexpr int kRxBlock = 256;
-constexpr int kRxWave = 64;
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-#define AIPSTACK_RXP_GLOBAL __attribute__((address_space(1)))
-typedef AIPSTACK_RXP_GLOBAL u32x4 g_line;
-typedef AIPSTACK_RXP_GLOBAL u32x2 g_pair;
-typedef const AIPSTACK_RXP_GLOBAL uint32_t g_cu32_any __attribute__((aligned(1)));
-typedef const AIPSTACK_RXP_GLOBAL u32x4 g_entry __attribute__((aligned(8)));
-
-__device__ __forceinline__ uint64_t rxp_uniform64(uint64_t v) {
-    return ((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(v >> 32)) << 32) |
-           __builtin_amdgcn_readfirstlane((uint32_t)v);
-}
 
 // Frame i's start address and length, as Rx verify takes them.
 struct CsrFrames {
@@ -67,7 +52,7 @@ struct SlotFrames {
 struct FrameLoad {
     uint64_t S;
     __device__ __forceinline__ uint32_t operator()(uint32_t off) const {
-        return *reinterpret_cast<g_cu32_any *>(S + off);
+        return *reinterpret_cast<global_t<const uint32_t, 1> *>(S + off);
     }
 };
 
@@ -79,7 +64,8 @@ __device__ __forceinline__ uint32_t rxp_lookup(const aipstack_tcp_pcb_key *__res
     uint64_t lo = 0, hi = n_pcbs;
     while (lo < hi) {
         const uint64_t mid = lo + ((hi - lo) >> 1);
-        const u32x4 e = *reinterpret_cast<g_entry *>((uint64_t)(uintptr_t)pcbs + mid * 16u);
+        const u32x4 e =
+            *reinterpret_cast<global_t<const u32x4, 8> *>((uint64_t)(uintptr_t)pcbs + mid * 16u);
         aipstack_tcp_pcb_key k;
         k.local_addr = e.x;
         k.remote_addr = e.y;
@@ -95,16 +81,13 @@ __device__ __forceinline__ uint32_t rxp_lookup(const aipstack_tcp_pcb_key *__res
 
 // LINES: d_segs is 16-byte aligned.
 template <class Frames, bool LINES>
-__global__ __launch_bounds__(kRxBlock) void tcprx_parse_kernel(
+__global__ __launch_bounds__(kBlock) void tcprx_parse_kernel(
     const Frames fr, uint64_t n, const aipstack_tcp_pcb_key *__restrict__ pcbs, uint64_t n_pcbs,
     uint8_t *__restrict__ verdict, uint64_t segs, uint32_t *__restrict__ pcb) {
-    __shared__ u32x4 tile[LINES ? kRxBlock / kRxWave : 1][LINES ? kRxWave : 1][2];
-    const uint64_t step = (uint64_t)gridDim.x * kRxBlock;
-    const uint32_t lane = threadIdx.x & (kRxWave - 1);
-    const uint32_t wave = threadIdx.x >> 6;
-    const uint64_t first = (uint64_t)blockIdx.x * kRxBlock + (threadIdx.x & ~(uint32_t)(kRxWave - 1));
-    for (uint64_t base = rxp_uniform64(first); base < n; base += step) {
-        const uint64_t i = base + lane;
+    __shared__ LineTiles<2, LINES> tile;
+    const WaveStride ws;
+    for (uint64_t base = uniform64(ws.first); base < n; base += ws.step) {
+        const uint64_t i = base + ws.lane;
         const bool active = i < n;
         uint32_t w[8];
 #pragma unroll
@@ -127,26 +110,15 @@ __global__ __launch_bounds__(kRxBlock) void tcprx_parse_kernel(
         }
         if (active) __builtin_nontemporal_store(cookie, &pcb[i]);
         if constexpr (LINES) {
-            // record `lane` into LDS, then store instruction r takes the quads of records
-            // 32r .. 32r+31 in memory order: 64 lanes x 16 bytes = 1 KiB contiguous
-            tile[wave][lane][0] = u32x4{w[0], w[1], w[2], w[3]};
-            tile[wave][lane][1] = u32x4{w[4], w[5], w[6], w[7]};
-            __builtin_amdgcn_wave_barrier();
-#pragma unroll
-            for (uint32_t r = 0; r < 2; ++r) {
-                const uint32_t rec = 32u * r + (lane >> 1), q = lane & 1u;
-                const u32x4 v = tile[wave][rec][q];
-                if (base + rec < n)
-                    __builtin_nontemporal_store(
-                        v, reinterpret_cast<g_line *>(segs + (base + rec) * 32u + q * 16u));
-            }
-            __builtin_amdgcn_wave_barrier();
+            // the records below n
+            store_wave_lines<2>(tile[ws.wave], ws.lane, segs, base,
+                                __builtin_amdgcn_ballot_w64(active), w);
         } else if (active) {
 #pragma unroll
             for (uint32_t q = 0; q < 4; ++q)
                 __builtin_nontemporal_store(
                     u32x2{w[2 * q], w[2 * q + 1]},
-                    reinterpret_cast<g_pair *>(segs + i * 32u + q * 8u));
+                    reinterpret_cast<global_t<u32x2> *>(segs + i * 32u + q * 8u));
         }
     }
 }
@@ -154,16 +126,15 @@ __global__ __launch_bounds__(kRxBlock) void tcprx_parse_kernel(
 template <class Frames>
 int launch_parse(const Frames &fr, uint64_t n, const aipstack_tcp_pcb_key *d_pcbs, uint64_t n_pcbs,
                  uint8_t *d_verdict, aipstack_tcp_rx_seg *d_segs, uint32_t *d_pcb, hipStream_t s) {
-    const int cus = device_cu_count(s);
-    if (cus <= 0) return AIPSTACK_CHKSUM_EHIP;
-    const uint64_t want = (n + kRxBlock - 1) / kRxBlock, most = tuning_aux_blocks(cus);
-    const unsigned blocks = (unsigned)(want < most ? want : most);
+    unsigned blocks;
+    const int st = lane_pass_blocks(n, s, &blocks);
+    if (st != AIPSTACK_CHKSUM_OK) return st;
     const uint64_t segs = (uint64_t)(uintptr_t)d_segs;
     if ((segs & 15u) == 0u)
-        hipLaunchKernelGGL((tcprx_parse_kernel<Frames, true>), dim3(blocks), dim3(kRxBlock), 0, s, fr,
+        hipLaunchKernelGGL((tcprx_parse_kernel<Frames, true>), dim3(blocks), dim3(kBlock), 0, s, fr,
                            n, d_pcbs, n_pcbs, d_verdict, segs, d_pcb);
     else
-        hipLaunchKernelGGL((tcprx_parse_kernel<Frames, false>), dim3(blocks), dim3(kRxBlock), 0, s,
+        hipLaunchKernelGGL((tcprx_parse_kernel<Frames, false>), dim3(blocks), dim3(kBlock), 0, s,
                            fr, n, d_pcbs, n_pcbs, d_verdict, segs, d_pcb);
     return check_hip(hipGetLastError());
 }

@@ -31,41 +31,16 @@
 
 #include "aipstack_amd/chksum.h"
 #include "chksum_internal.h"
+#include "lane_pass.h"
 #include "tcpseg_common.h"
 
 namespace aipstack_amd {
 namespace {
 
-constexpr int kTsBlock = 256;
-constexpr int kTsWave = 64;
-
 // The record of segment i (workspace, 8 bytes): bits 0-39 the burst that owns it, 40-55 the
 // IPv4 header checksum, 56 = valid (emit the slot; else status AIPSTACK_TX_BURST_INVALID).
 constexpr uint64_t kRecBurstMask = (1ull << 40) - 1u;
 constexpr uint64_t kRecValid = 1ull << 56;
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-#define AIPSTACK_TS_GLOBAL __attribute__((address_space(1)))
-typedef AIPSTACK_TS_GLOBAL u32x4 g_line;
-typedef AIPSTACK_TS_GLOBAL u32x4 g_quad_any __attribute__((aligned(1)));
-typedef AIPSTACK_TS_GLOBAL uint32_t g_u32_any __attribute__((aligned(1)));
-typedef AIPSTACK_TS_GLOBAL uint16_t g_u16_any __attribute__((aligned(1)));
-typedef AIPSTACK_TS_GLOBAL uint8_t g_u8;
-
-__device__ __forceinline__ uint32_t ts_bswap16(uint32_t x) {
-    return ((x & 0xFFu) << 8) | ((x >> 8) & 0xFFu);
-}
-
-// x mod 0xFFFF with a nonzero multiple as 0xFFFF: zero only for x = 0.
-__device__ __forceinline__ uint32_t ts_fold16(uint32_t x) {
-    x = (x & 0xFFFFu) + (x >> 16);
-    return (x & 0xFFFFu) + (x >> 16);
-}
-
-__device__ __forceinline__ uint64_t ts_uniform64(uint64_t v) {
-    return ((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(v >> 32)) << 32) |
-           __builtin_amdgcn_readfirstlane((uint32_t)v);
-}
 
 // The first j in [lo, hi] with idx[j] > i (hi if there is none); reads entries in [lo, hi).
 __device__ __forceinline__ uint64_t ts_upper_bound(const uint64_t *__restrict__ idx, uint64_t lo,
@@ -128,8 +103,8 @@ __device__ __forceinline__ uint32_t ts_addr_halves(const Template &h) {
 // addresses from the template, total length and ident per segment, the field as 0.
 __device__ __forceinline__ uint32_t ts_ip_checksum(const Template &h, const SegWords &w) {
     const uint32_t le = (h.t[3] >> 16) + (h.t[5] & 0xFFFFu) + (h.t[5] >> 16) + ts_addr_halves(h);
-    const uint32_t be = ts_bswap16(ts_fold16(le)) + w.total_len + w.ident;
-    return ~ts_fold16(be) & 0xFFFFu;
+    const uint32_t be = bswap16(fold16(le)) + w.total_len + w.ident;
+    return ~fold16(be) & 0xFFFFu;
 }
 
 // The State the data chain is resumed from: the pseudo-header (addresses, protocol 6, tcp_len)
@@ -138,7 +113,7 @@ __device__ __forceinline__ uint32_t ts_ip_checksum(const Template &h, const SegW
 __device__ __forceinline__ uint32_t ts_l4_seed(const Template &h, const SegWords &w) {
     const uint32_t le = ts_addr_halves(h) + (h.t[8] >> 16) + (h.t[9] & 0xFFFFu) + (h.t[10] >> 16) +
                         (h.t[11] & 0xFFFFu) + (h.t[12] & 0xFFFFu) + (h.t[13] & 0xFFFFu);
-    return ts_bswap16(ts_fold16(le)) + 6u + (20u + w.len) + (w.seq >> 16) + (w.seq & 0xFFFFu) +
+    return bswap16(fold16(le)) + 6u + (20u + w.len) + (w.seq >> 16) + (w.seq & 0xFFFFu) +
            w.offset_flags;
 }
 
@@ -217,25 +192,23 @@ __device__ __forceinline__ void ts_plan_segment(
     __builtin_nontemporal_store(rec, &records[i]);
 }
 
-__global__ __launch_bounds__(kTsBlock) void tcpseg_plan_kernel(
+__global__ __launch_bounds__(kBlock) void tcpseg_plan_kernel(
     const aipstack_tcp_burst *__restrict__ bursts, const uint64_t *__restrict__ seg_index,
     const uint64_t *__restrict__ chunk_base, uint64_t n_bursts, uint64_t n_segments,
     uint64_t n_chunks, uint64_t *__restrict__ chunk_addr, uint32_t *__restrict__ chunk_len,
     uint64_t *__restrict__ chunk_index, uint32_t *__restrict__ seeds,
     uint64_t *__restrict__ records) {
-    const uint64_t step = (uint64_t)gridDim.x * kTsBlock;
-    const uint32_t lane = threadIdx.x & (kTsWave - 1);
-    const uint64_t first = (uint64_t)blockIdx.x * kTsBlock + (threadIdx.x & ~(uint32_t)(kTsWave - 1));
+    const WaveStride ws;
     if (blockIdx.x == 0 && threadIdx.x == 0)
         __builtin_nontemporal_store(n_chunks, &chunk_index[n_segments]);
-    for (uint64_t base = ts_uniform64(first); base < n_segments; base += step) {
+    for (uint64_t base = uniform64(ws.first); base < n_segments; base += ws.step) {
         // The wave's 64 segments mostly share one or two bursts: the owners of its first and
         // last segment are found with wave-uniform searches, and each lane searches only
         // between them (no step at all when they agree).
-        const uint64_t last = base + (kTsWave - 1) < n_segments ? base + (kTsWave - 1) : n_segments - 1;
-        const uint64_t j0 = ts_uniform64(ts_upper_bound(seg_index, 0, n_bursts + 1, base));
-        const uint64_t j1 = ts_uniform64(ts_upper_bound(seg_index, j0, n_bursts + 1, last));
-        const uint64_t i = base + lane;
+        const uint64_t last = base + (kWave - 1) < n_segments ? base + (kWave - 1) : n_segments - 1;
+        const uint64_t j0 = uniform64(ts_upper_bound(seg_index, 0, n_bursts + 1, base));
+        const uint64_t j1 = uniform64(ts_upper_bound(seg_index, j0, n_bursts + 1, last));
+        const uint64_t i = base + ws.lane;
         if (i >= n_segments) continue;
         if (j0 == j1 && j0 >= 1 && j0 <= n_bursts) {
             const uint64_t b = j0 - 1;  // uniform: descriptor and index loads are shared
@@ -264,7 +237,7 @@ __global__ __launch_bounds__(kTsBlock) void tcpseg_plan_kernel(
     }
     // Bursts that break the contract: their chunk entries are emptied (length 0 at address 0),
     // whether or not the index gives them a segment.
-    for (uint64_t b = (uint64_t)blockIdx.x * kTsBlock + threadIdx.x; b < n_bursts; b += step) {
+    for (uint64_t b = (uint64_t)blockIdx.x * kBlock + threadIdx.x; b < n_bursts; b += ws.step) {
         const BurstRange r = ts_range(seg_index, chunk_base, b);
         if (ts_burst_ok(tcp_burst_shape(bursts[b]), r, n_segments, n_chunks)) continue;
         uint64_t c0, cnt;
@@ -275,17 +248,14 @@ __global__ __launch_bounds__(kTsBlock) void tcpseg_plan_kernel(
 
 // Emit pass. LINES: hdr_stride == 64 and the ring starts on a 64-byte boundary.
 template <bool LINES>
-__global__ __launch_bounds__(kTsBlock) void tcpseg_emit_kernel(
+__global__ __launch_bounds__(kBlock) void tcpseg_emit_kernel(
     const aipstack_tcp_burst *__restrict__ bursts, const uint64_t *__restrict__ seg_index,
     const uint64_t *__restrict__ records, const uint16_t *__restrict__ sums, uint64_t hdr_base,
     uint64_t hdr_stride, uint8_t *__restrict__ status, uint64_t n_segments) {
-    __shared__ u32x4 tile[LINES ? kTsBlock / kTsWave : 1][LINES ? kTsWave : 1][4];
-    const uint64_t step = (uint64_t)gridDim.x * kTsBlock;
-    const uint32_t lane = threadIdx.x & (kTsWave - 1);
-    const uint32_t wave = threadIdx.x >> 6;
-    const uint64_t first = (uint64_t)blockIdx.x * kTsBlock + (threadIdx.x & ~(uint32_t)(kTsWave - 1));
-    for (uint64_t base = ts_uniform64(first); base < n_segments; base += step) {
-        const uint64_t i = base + lane;
+    __shared__ LineTiles<4, LINES> tile;
+    const WaveStride ws;
+    for (uint64_t base = uniform64(ws.first); base < n_segments; base += ws.step) {
+        const uint64_t i = base + ws.lane;
         const bool active = i < n_segments;
         const uint64_t rec = active ? __builtin_nontemporal_load(&records[i]) : 0u;
         const bool valid = (rec & kRecValid) != 0u;
@@ -303,44 +273,30 @@ __global__ __launch_bounds__(kTsBlock) void tcpseg_emit_kernel(
             const uint32_t l4chk = ~(uint32_t)__builtin_nontemporal_load(&sums[i]) & 0xFFFFu;
 #pragma unroll
             for (int q = 0; q < 14; ++q) o[q] = h.t[q];
-            o[4] = ts_bswap16(w.total_len) | ts_bswap16(w.ident) << 16;
-            o[6] = ts_bswap16(ipchk) | (h.t[6] & 0xFFFF0000u);
-            o[9] = (h.t[9] & 0xFFFFu) | ts_bswap16(w.seq >> 16) << 16;
-            o[10] = ts_bswap16(w.seq & 0xFFFFu) | (h.t[10] & 0xFFFF0000u);
-            o[11] = (h.t[11] & 0xFFFFu) | ts_bswap16(w.offset_flags) << 16;
-            o[12] = (h.t[12] & 0xFFFFu) | ts_bswap16(l4chk) << 16;
+            o[4] = bswap16(w.total_len) | bswap16(w.ident) << 16;
+            o[6] = bswap16(ipchk) | (h.t[6] & 0xFFFF0000u);
+            o[9] = (h.t[9] & 0xFFFFu) | bswap16(w.seq >> 16) << 16;
+            o[10] = bswap16(w.seq & 0xFFFFu) | (h.t[10] & 0xFFFF0000u);
+            o[11] = (h.t[11] & 0xFFFFu) | bswap16(w.offset_flags) << 16;
+            o[12] = (h.t[12] & 0xFFFFu) | bswap16(l4chk) << 16;
             o[13] = h.t[13] & 0xFFFFu;
         }
         if (active)
             status[i] = (uint8_t)(valid ? AIPSTACK_RX_ACCEPT : AIPSTACK_TX_BURST_INVALID);
         if constexpr (LINES) {
-            // slot `lane` into LDS, then store instruction r takes the quads of slots
-            // 16r .. 16r+15 in memory order: 64 lanes x 16 bytes = 1 KiB contiguous
-            const uint64_t ok = __builtin_amdgcn_ballot_w64(valid);
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-                tile[wave][lane][q] = u32x4{o[4 * q], o[4 * q + 1], o[4 * q + 2], o[4 * q + 3]};
-            __builtin_amdgcn_wave_barrier();
-#pragma unroll
-            for (uint32_t r = 0; r < 4; ++r) {
-                const uint32_t slot = 16u * r + (lane >> 2), q = lane & 3u;
-                const u32x4 v = tile[wave][slot][q];
-                if ((ok >> slot) & 1ull)  // (a valid slot is below n_segments)
-                    __builtin_nontemporal_store(
-                        v, reinterpret_cast<g_line *>(hdr_base + (base + slot) * 64u + q * 16u));
-            }
-            __builtin_amdgcn_wave_barrier();
+            const uint64_t ok = __builtin_amdgcn_ballot_w64(valid);  // (valid: below n_segments)
+            store_wave_lines<4>(tile[ws.wave], ws.lane, hdr_base, base, ok, o);
         } else if (valid) {
             const uint64_t P = hdr_base + i * hdr_stride;
 #pragma unroll
             for (int q = 0; q < 3; ++q)
-                *reinterpret_cast<g_quad_any *>(P + 16u * q) =
+                *reinterpret_cast<global_t<u32x4, 1> *>(P + 16u * q) =
                     u32x4{o[4 * q], o[4 * q + 1], o[4 * q + 2], o[4 * q + 3]};
-            *reinterpret_cast<g_u32_any *>(P + 48u) = o[12];
-            *reinterpret_cast<g_u16_any *>(P + 52u) = (uint16_t)o[13];
+            *reinterpret_cast<global_t<uint32_t, 1> *>(P + 48u) = o[12];
+            *reinterpret_cast<global_t<uint16_t, 1> *>(P + 52u) = (uint16_t)o[13];
             const uint32_t end = hdr_stride < 64u ? (uint32_t)hdr_stride : 64u;
             for (uint32_t z = AIPSTACK_TCP_SEGMENT_HEADER; z < end; ++z)
-                *reinterpret_cast<g_u8 *>(P + z) = 0u;
+                *reinterpret_cast<global_t<uint8_t> *>(P + z) = 0u;
         }
     }
 }
@@ -363,15 +319,14 @@ extern "C" int aipstack_tcp_tx_segment(const aipstack_tcp_burst *d_bursts,
                                        d_chunk_index, d_status, d_workspace, workspace_bytes);
     if (st != AIPSTACK_CHKSUM_OK) return st;
     const hipStream_t s = (hipStream_t)stream;
-    const int cus = device_cu_count(s);
-    if (cus <= 0) return AIPSTACK_CHKSUM_EHIP;
     const uint64_t n = n_segments;
+    unsigned blocks;
+    st = lane_pass_blocks(n, s, &blocks);
+    if (st != AIPSTACK_CHKSUM_OK) return st;
     uint64_t *records = static_cast<uint64_t *>(d_workspace);
     uint32_t *seeds = reinterpret_cast<uint32_t *>(records + n);
     uint16_t *sums = reinterpret_cast<uint16_t *>(seeds + n);
-    const uint64_t want = (n + kTsBlock - 1) / kTsBlock, most = tuning_aux_blocks(cus);
-    const unsigned blocks = (unsigned)(want < most ? want : most);
-    hipLaunchKernelGGL(tcpseg_plan_kernel, dim3(blocks), dim3(kTsBlock), 0, s, d_bursts,
+    hipLaunchKernelGGL(tcpseg_plan_kernel, dim3(blocks), dim3(kBlock), 0, s, d_bursts,
                        d_seg_index, d_chunk_base, n_bursts, n, n_chunks, d_chunk_addr, d_chunk_len,
                        d_chunk_index, seeds, records);
     st = check_hip(hipGetLastError());
@@ -381,10 +336,10 @@ extern "C" int aipstack_tcp_tx_segment(const aipstack_tcp_burst *d_bursts,
     if (st != AIPSTACK_CHKSUM_OK) return st;
     const uint64_t base = (uint64_t)(uintptr_t)d_hdr;
     if (hdr_stride == 64u && (base & 63u) == 0u)
-        hipLaunchKernelGGL(tcpseg_emit_kernel<true>, dim3(blocks), dim3(kTsBlock), 0, s, d_bursts,
+        hipLaunchKernelGGL(tcpseg_emit_kernel<true>, dim3(blocks), dim3(kBlock), 0, s, d_bursts,
                            d_seg_index, records, sums, base, hdr_stride, d_status, n);
     else
-        hipLaunchKernelGGL(tcpseg_emit_kernel<false>, dim3(blocks), dim3(kTsBlock), 0, s, d_bursts,
+        hipLaunchKernelGGL(tcpseg_emit_kernel<false>, dim3(blocks), dim3(kBlock), 0, s, d_bursts,
                            d_seg_index, records, sums, base, hdr_stride, d_status, n);
     return check_hip(hipGetLastError());
 }
