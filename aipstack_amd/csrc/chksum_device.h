@@ -523,37 +523,11 @@ __device__ __forceinline__ void wave_sum_n(uint32_t (&v)[N]) {
 
 // No per-packet adjustment (see sum_lane_packets).
 struct NoMaskHook {
-    static constexpr bool kField = false;
     template <class PK>
     __device__ __forceinline__ void issue(int, int) {}
     template <class PK>
     __device__ __forceinline__ void apply(int, PK &, int) {}
-    __device__ __forceinline__ int row_field(int) { return -64; }
 };
-
-// ---------------------------------------------------------------------------------
-// Row mode: packets of at most 16 aligned segments (<= 241 bytes at worst alignment),
-// four per wave instruction. Row r (lanes 16r..16r+15) holds one packet; lane k of the
-// row loads the packet's segment k with a per-lane address (its row's LaneMeta fetched
-// with ds_bpermute), masks its own head/tail bytes in VALU, and the 16 lanes of a row are
-// added by a 4-step row DPP scan. Same sum as the wave mode (an end-around-carry sum of
-// the masked little-endian dwords), at a quarter of the per-packet instructions.
-// ---------------------------------------------------------------------------------
-constexpr uint32_t kRowSegs = 16;
-
-// Row groups (of four packets) a kernel keeps in flight; 0 = no row mode. Per kernel
-// family, measured; overridable at build time for experiments.
-#ifndef AIPSTACK_ROWS_STRIDED
-#define AIPSTACK_ROWS_STRIDED 0
-#endif
-#ifndef AIPSTACK_ROWS_CSR
-#define AIPSTACK_ROWS_CSR 0
-#endif
-#ifndef AIPSTACK_ROWS_FRAMES
-#define AIPSTACK_ROWS_FRAMES 0
-#endif
-
-__device__ u32x4 g_zero_segment;  // a valid address for rows without a packet
 
 // Keep bytes [a, b) of a little-endian dword (a, b clamped to 0..4).
 __device__ __forceinline__ uint32_t dword_keep(int a, int b) {
@@ -562,133 +536,35 @@ __device__ __forceinline__ uint32_t dword_keep(int a, int b) {
     return b > a ? ((0xFFFFFFFFu >> (32 - 8 * (b - a))) << (8 * a)) : 0u;
 }
 
-// Edge / boundary segments (the few per chunk read outside the stream): their cache policy.
-// 0 = default (the stream reads the same line again and finds it in L2), 1 = nontemporal.
-#ifndef AIPSTACK_EDGE_NT
-#define AIPSTACK_EDGE_NT 0
-#endif
-constexpr bool kEdgeNT = AIPSTACK_EDGE_NT != 0;
-
+// Edge / boundary segments (the few per chunk read outside the stream) load with the default
+// cache policy: the stream reads the same line again and finds it in L2.
 // `nt` (wave-uniform, run time): the AIPSTACK_CHKSUM_JUST_WRITTEN hint -- on lines ordinary
 // stores wrote since they were last read, a cached read is the expensive one.
 __device__ __forceinline__ u32x4 load_edge_segment(uint64_t addr, bool nt = false) {
     typedef __attribute__((address_space(1))) const u32x4 gseg;
     const gseg *p = (const gseg *)addr;
-    if (kEdgeNT || nt)
+    if (nt)
         return __builtin_nontemporal_load(p);
     else
         return *p;
 }
 __device__ __forceinline__ u32x4 load_edge_segment(__amdgpu_buffer_rsrc_t rsrc, uint32_t voff,
                                                    bool nt = false) {
-    return (kEdgeNT || nt) ? load_segment<true>(rsrc, voff, 0u) : load_segment<false>(rsrc, voff, 0u);
+    return nt ? load_segment<true>(rsrc, voff, 0u) : load_segment<false>(rsrc, voff, 0u);
 }
 
-template <bool NT>
-__device__ __forceinline__ u32x4 load_lane_segment(uint64_t addr) {
-    const u32x4 *p = reinterpret_cast<const u32x4 *>(addr);
-    if constexpr (NT)
-        return __builtin_nontemporal_load(p);
-    else
-        return *p;
-}
-
-template <int kRowGroups, bool NT, class Hook>
-__device__ __forceinline__ uint32_t sum_row_packets(const LaneMeta &meta, uint64_t todo,
-                                                    int lane, uint32_t sums, Hook &hook) {
-    const int row = lane >> 4, k = lane & 15;
-    while (todo) {
-        u32x4 v[kRowGroups];
-        int jr[kRowGroups][4];
-        uint32_t packed_l[kRowGroups];
-        int src_l[kRowGroups];
-#pragma unroll
-        for (int g = 0; g < kRowGroups; ++g) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const bool valid = todo != 0;
-                jr[g][r] = valid ? (int)__builtin_ctzll(todo) : -1;
-                todo &= todo - 1;
-            }
-            int src = jr[g][0];
-            src = row == 1 ? jr[g][1] : src;
-            src = row == 2 ? jr[g][2] : src;
-            src = row == 3 ? jr[g][3] : src;
-            const int from = max(src, 0) << 2;
-            const uint32_t lo = (uint32_t)__builtin_amdgcn_ds_bpermute(from, (int)meta.a0_lo);
-            const uint32_t hi = (uint32_t)__builtin_amdgcn_ds_bpermute(from, (int)meta.a0_hi);
-            const uint32_t packed = (uint32_t)__builtin_amdgcn_ds_bpermute(from, (int)meta.packed);
-            const uint32_t nseg = packed >> 9;  // 1..16 for a row packet
-            const uint32_t kk = min((uint32_t)k, nseg - 1u);
-            const uint64_t addr = src >= 0
-                                      ? ((((uint64_t)hi << 32) | lo) + 16u * (uint64_t)kk)
-                                      : (uint64_t)(uintptr_t)&g_zero_segment;
-            v[g] = load_lane_segment<NT>(addr);
-            packed_l[g] = packed;
-            src_l[g] = src;
-        }
-        uint32_t part[kRowGroups];
-#pragma unroll
-        for (int g = 0; g < kRowGroups; ++g) {
-            const uint32_t packed = packed_l[g];
-            const int nseg = (int)(packed >> 9);
-            const bool in = src_l[g] >= 0 && k < nseg;
-            const int lo = k == 0 ? (int)(packed & 15u) : 0;
-            const int hi = k == nseg - 1 ? (int)((packed >> 4) & 31u) : 16;
-            int fx = -64;  // a 2-byte field summed as 0, bytes from the packet's A0
-            if constexpr (Hook::kField)
-                fx = hook.row_field(max(src_l[g], 0)) - 16 * k;
-            Eac a;
-#pragma unroll
-            for (int d = 0; d < 4; ++d) {
-                uint32_t m = dword_keep(lo - 4 * d, hi - 4 * d);
-                if constexpr (Hook::kField)
-                    m &= ~dword_keep(fx - 4 * d, fx + 2 - 4 * d);
-                a.add(v[g][d] & (in ? m : 0u));
-            }
-            const uint32_t s0 = a.finish();
-            part[g] = (s0 & 0xFFFFu) + (s0 >> 16);  // < 2^17; 16 lanes < 2^21
-        }
-        // row sums: 4-step row scan, interleaved across the groups; lane 16r+15 = row r
-#define AIPSTACK_ROW_STEP(ctrl)                                                             \
-    _Pragma("unroll") for (int g = 0; g < kRowGroups; ++g)                                   \
-        part[g] += __builtin_amdgcn_update_dpp(0u, part[g], ctrl, 0xF, 0xF, false);
-        AIPSTACK_ROW_STEP(0x111)
-        AIPSTACK_ROW_STEP(0x112)
-        AIPSTACK_ROW_STEP(0x114)
-        AIPSTACK_ROW_STEP(0x118)
-#undef AIPSTACK_ROW_STEP
-#pragma unroll
-        for (int g = 0; g < kRowGroups; ++g)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const uint32_t t = (uint32_t)__builtin_amdgcn_readlane(part[g], 16 * r + 15);
-                sums = (lane == jr[g][r]) ? t : sums;
-            }
-    }
-    return sums;
-}
-
-// The packets of a 64-packet chunk whose lanes are set in `todo` (wave-uniform): with
-// RG > 0, those of at most 16 segments four per wave instruction (sum_row_packets, RG
-// groups in flight); the others each
+// The packets of a 64-packet chunk whose lanes are set in `todo` (wave-uniform), each
 // summed by the whole wave with P packets' loads in flight; lane j receives packet j's
 // exact halves-sum (< 2^24; 0 iff all its bytes are 0), other lanes 0. `meta` is the
 // per-lane LaneMeta. hook.issue(q, j) runs when packet j's loads are issued into slot q,
 // hook.apply(q, pk, lane) just before slot q is reduced (e.g. to mask a field).
-template <int U, int P, int RG, bool NT, class Hook>
+// (Removed: row mode, packets of at most 16 segments summed four per wave instruction; off in
+// every kernel family since it was measured; docs/HISTORY.md, code last in b66da65.)
+template <int U, int P, bool NT, class Hook>
 __device__ __forceinline__ uint32_t sum_lane_packets(const LaneMeta &meta, uint64_t todo,
                                                      int lane, uint32_t voff,
                                                      uint32_t not_lane0, Hook &hook) {
     uint32_t sums = 0;
-    if constexpr (RG > 0) {
-        const uint64_t small =
-            todo & __builtin_amdgcn_ballot_w64((meta.packed >> 9) <= kRowSegs);
-        if (small) {
-            sums = sum_row_packets<RG, NT>(meta, small, lane, sums, hook);
-            todo &= ~small;
-        }
-    }
     while (todo) {
         PacketLoad<U, NT> pk[P];
         int jq[P];
@@ -790,10 +666,8 @@ struct NoStreamHook {
 // DB (round 4): the next group of U windows is issued before the current one is summed (two
 // register sets, as the gathered stream does, §5.2 of DESIGN.md), so a wave always has
 // U..2U windows in flight; without it the next group goes out only after the current one is
-// summed.
-#ifndef AIPSTACK_STREAM_DB  // the checksum batches' stream mode with DB (A/B build switch;
-#define AIPSTACK_STREAM_DB 0  // round 4: A 233.2 vs 233.6 us, so off)
-#endif
+// summed. The short runs (SU > 8) and the frame kernels use it; the checksum batches' stream
+// mode of 2 / 4 / 8 windows does not (round 4: config A 233.2 us with DB against 233.6 without).
 // GL (round 5, the short runs' experiment switch): global_load_dwordx4 from the wave-uniform
 // run start plus a 32-bit lane offset (the gathered stream's load form) instead of a buffer
 // descriptor; segments past the run re-read its last segment and are summed as 0.
@@ -973,28 +847,10 @@ __device__ __forceinline__ int wave_max_scan(int v) {
 // Exact halves-sum of lane j's own short chunk [a, a + l) (l <= 128 B here: at most 9
 // segments), read by the lane itself: its aligned 16-byte segments, nontemporal, the bytes
 // outside the chunk masked off; kmax = the wave's largest segment count (uniform). The chain
-// kernel's header nodes (round 6, chain runs): side by side in memory, adjacent lanes read
-// adjacent segments, so one wave instruction fetches whole lines.
-__device__ __forceinline__ uint32_t sum_own_short_chunk(uint64_t a, uint32_t l, uint32_t kmax) {
-    typedef __attribute__((address_space(1))) const u32x4 gseg;
-    const uint32_t rs = (uint32_t)a & 15u;
-    const uint32_t nsg = l ? (rs + l + 15u) >> 4 : 0u;
-    const uint32_t te = ((rs + l - 1u) & 15u) + 1u;  // the chunk's end in its last segment
-    const gseg *p = (const gseg *)(a & ~(uint64_t)15);
-    uint32_t acc = 0;
-    for (uint32_t k = 0; k < kmax; ++k) {
-        if (k < nsg) {
-            const u32x4 x = __builtin_nontemporal_load(p + k);
-            const int lo = k == 0 ? (int)rs : 0, hi = k + 1 == nsg ? (int)te : 16;
-#pragma unroll
-            for (int d = 0; d < 4; ++d) acc = halves(x[d] & dword_keep(lo - 4 * d, hi - 4 * d), acc);
-        }
-    }
-    return acc;
-}
-
-// The same with the chunk's first two segments already loaded (x0, x1: issued early, so that
-// their latency hides behind other loads); segments 2.. are loaded here.
+// kernel's header nodes (round 6, chain column runs): side by side in memory, adjacent lanes
+// read adjacent segments, so one wave instruction fetches whole lines. The chunk's first two
+// segments come already loaded (x0, x1: issued early, so that their latency hides behind other
+// loads); segments 2.. are loaded here.
 __device__ __forceinline__ uint32_t sum_short_chunk_from(const u32x4 &x0, const u32x4 &x1,
                                                          uint64_t a, uint32_t l, uint32_t kmax) {
     typedef __attribute__((address_space(1))) const u32x4 gseg;
@@ -1272,7 +1128,7 @@ __device__ __forceinline__ uint32_t sum_segtab_chunk(uint64_t S, uint64_t E, int
     const uint32_t rel = (uint32_t)(S - A);
     const uint32_t g = rel >> 4, o = rel & 15u;
     u32x4 bseg = {0u, 0u, 0u, 0u};
-    if (lane <= cnt && o != 0u) bseg = load_segment<kEdgeNT>(rsrc, g * 16u, 0u);
+    if (lane <= cnt && o != 0u) bseg = load_segment<false>(rsrc, g * 16u, 0u);
     constexpr int U = 8;
     u32x4 va[U], vb[U];
     auto issue = [&](u32x4 (&v)[U], uint32_t w) {
@@ -1413,28 +1269,23 @@ __device__ __forceinline__ uint32_t sum_slot_windows(uint64_t S, uint64_t E, int
 // Stream mode for one chunk (stream_ok). Lane j < cnt holds packet j = [S, E); returns
 // lane j's exact halves-sum (0 on lanes >= cnt).
 // SU <= 8: SU windows issued together, the next group after the current one is summed (rounds
-// 1-4). SU > 8 (round 5, short runs): groups of AIPSTACK_SHORT_RUN_WINDOWS windows,
+// 1-4). SU > 8 (round 5, short runs): groups of kShortRunWindows windows,
 // double-buffered -- the next group goes out before the current one is summed, so a wave of
 // one short chunk issues all of its ~12 KiB before it sums the first window (the gathered
 // stream's issue pattern, without its per-window owner lookup and address arithmetic).
-// Short runs' stream prefixes: packet starts' partial segments loaded per lane up front (1) or
-// taken from the stream (0). Driver protocol (profiles/r05/edge): config C 247.9-250.1 us with
-// the loads against 240.5-243.5 without (2 M extra loads); A in stream prefixes 223.4-224.2
-// against 230.3-230.5 (A's default, column runs, does this already). A/B build switch.
-#ifndef AIPSTACK_STREAM_EDGE_LOADS
-#define AIPSTACK_STREAM_EDGE_LOADS 0
-#endif
+// Packet starts' partial segments are taken from the stream. Tried in round 5 and removed
+// (code last in b66da65): loading them per lane up front, config C 247.9-250.1 us with the
+// loads against 240.5-243.5 without (2 M extra loads, profiles/r05/edge); A in stream prefixes
+// 223.4-224.2 against 230.3-230.5 (A's default, column runs, does this already).
+// Short runs' windows per group, double-buffered: config C under the driver's protocol
+// 241.7-242.5 us at 6 against 242.1-249.3 at 8 and 247.3-248.4 at 4 (profiles/r05/sru):
+// ~12 KiB chunks load 12 windows instead of 16.
+constexpr int kShortRunWindows = 6;
 template <int SU, bool NT>
 __device__ __forceinline__ uint32_t sum_stream_chunk(uint64_t S, uint64_t E, int lane, int cnt,
                                                      uint32_t voff) {
-    constexpr bool kDb = SU > 8 || AIPSTACK_STREAM_DB != 0;
-// Short runs' windows per group, double-buffered (A/B build switch): config C under the
-// driver's protocol 241.7-242.5 us at 6 against 242.1-249.3 at 8 and 247.3-248.4 at 4
-// (profiles/r05/sru): ~12 KiB chunks load 12 windows instead of 16.
-#ifndef AIPSTACK_SHORT_RUN_WINDOWS
-#define AIPSTACK_SHORT_RUN_WINDOWS 6
-#endif
-    constexpr int U = SU > 8 ? AIPSTACK_SHORT_RUN_WINDOWS : SU;
+    constexpr bool kDb = SU > 8;
+    constexpr int U = SU > 8 ? kShortRunWindows : SU;
     constexpr bool kGl = SU == 32;  // (SU 32: SU 16 through global loads, StreamRun GL)
     // X1 = end of the chunk's last packet; lanes past the batch sit at X1 (empty)
     const int lastl = cnt - 1;
@@ -1449,24 +1300,8 @@ __device__ __forceinline__ uint32_t sum_stream_chunk(uint64_t S, uint64_t E, int
     StreamRun<U, NT, U, kDb, kGl> run;
     const uint64_t bs[1] = {S};
     uint32_t hb[1], hx;
-    if constexpr (AIPSTACK_STREAM_EDGE_LOADS && SU > 8) {
-        // Short runs (device memory only): H at each packet start's segment (one ds_bpermute
-        // per window with starts, no partial segment from the stream) plus the bytes of that
-        // segment below the start, from one segment load per lane before the stream (as column
-        // runs; the stream reads that line again later). A start at X1 (lanes past the batch,
-        // empty tail packets) is exact. Stream mode (SU <= 8) also reads host memory over the
-        // link, where the edge segment would cross it twice.
-        const uint64_t A = S0 & ~(uint64_t)15;
-        const uint32_t o = (uint32_t)S & 15u;
-        u32x4 bseg = {0u, 0u, 0u, 0u};
-        if (S != X1 && o != 0u) bseg = load_edge_segment(S & ~(uint64_t)15);
-        run.begin(A, X1, voff);
-        run.template prefixes<1, true>(bs, hb, hx, voff);
-        hb[0] += S != X1 ? halves_below_seg(bseg, o) : 0u;
-    } else {
-        run.begin(S0 & ~(uint64_t)15, X1, voff);
-        run.prefixes(bs, hb, hx, voff);
-    }
+    run.begin(S0 & ~(uint64_t)15, X1, voff);
+    run.prefixes(bs, hb, hx, voff);
     const uint32_t hn = from_next_lane(hb[0], hx, lane);  // H(S_{j+1}); lane 63: H(X1)
     return lane < cnt ? hn - hb[0] : 0u;
 }
@@ -1523,7 +1358,7 @@ __device__ __forceinline__ uint32_t sum_column_chunk(uint64_t S, uint64_t E, int
     uint32_t *const segs = rows + (MAXP + 1) * kWave;  // (CAPTURE) boundary j's segment: entry j
     u32x4 bseg = {0u, 0u, 0u, 0u};            // boundary j's segment (lanes 0..cnt, o != 0)
     if (!CAPTURE && lane <= cnt && o != 0u)
-        bseg = load_segment<kEdgeNT>(rsrc, (rel >> 4) * 16u, 0u);
+        bseg = load_segment<false>(rsrc, (rel >> 4) * 16u, 0u);
     u32x4 va[U], vb[U];
     auto issue = [&](u32x4 (&v)[U], uint32_t w) {
 #pragma unroll
@@ -1633,12 +1468,9 @@ __device__ __forceinline__ uint32_t sum_gapped_column_chunk(uint64_t s0, int lan
     u32x4 fseg = {0u, 0u, 0u, 0u}, lseg = {0u, 0u, 0u, 0u};
     if (lane < cnt && rs != 0u) fseg = load_edge_segment(rsrc, pkoff, edge_nt);
     if (lane < cnt && te != 16u) lseg = load_edge_segment(rsrc, pkoff + 16u * (ns - 1u), edge_nt);
-// windows per group (A/B build switch; A2K 228.9-229.7 us at 6 and 228.9-229.6 at 8,
-// profiles/r05/gcu)
-#ifndef AIPSTACK_GAPCOL_WINDOWS
-#define AIPSTACK_GAPCOL_WINDOWS 8
-#endif
-    constexpr int U = AIPSTACK_GAPCOL_WINDOWS;
+    // windows per group (A2K 228.9-229.7 us at 6 and 228.9-229.6 at 8, profiles/r05/gcu)
+    constexpr int kGapColWindows = 8;
+    constexpr int U = kGapColWindows;
     u32x4 va[U], vb[U];
     auto issue = [&](u32x4 (&v)[U], uint32_t w) {
 #pragma unroll

@@ -164,9 +164,9 @@ __global__ __launch_bounds__(kBlock) void chksum_batch_kernel(Desc desc, uint64_
             // one packet per wave, P in flight; empty packets are skipped
             const LaneMeta meta = lane_meta(lS, lE);
             NoMaskHook hook;
-            sums = sum_lane_packets<U, P, Desc::kCsr ? AIPSTACK_ROWS_CSR : AIPSTACK_ROWS_STRIDED,
-                                    NT>(meta, __builtin_amdgcn_ballot_w64((meta.packed >> 9) != 0),
-                                        lane, voff, not_lane0, hook);
+            sums = sum_lane_packets<U, P, NT>(
+                meta, __builtin_amdgcn_ballot_w64((meta.packed >> 9) != 0), lane, voff, not_lane0,
+                hook);
         }
         // Finalise the chunk's 64 results together (VALU, one packet per lane).
         uint32_t r = fold16(sums);
@@ -210,9 +210,6 @@ __global__ __launch_bounds__(kBlock) void chksum_batch_kernel(Desc desc, uint64_
 // ---------------------------------------------------------------------------------
 
 // A 16-bit store at any byte address (one global_store_short: gfx9 runs in unaligned mode).
-#ifndef AIPSTACK_CHAIN_FIELD_NT
-#define AIPSTACK_CHAIN_FIELD_NT 1
-#endif
 typedef uint16_t u16_any_align __attribute__((aligned(1)));
 
 // Second pass of the chain fill: chain i's checksum (from the chained batch's output) stored
@@ -226,13 +223,10 @@ __global__ __launch_bounds__(kBlock) void chain_field_scatter_kernel(
     const uint64_t stride = (uint64_t)gridDim.x * kBlock;
     for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
         const uint64_t fa = fields[i];
-#if AIPSTACK_CHAIN_FIELD_NT  // nontemporal field stores (round 6): the header lines they write
-                             // carry no first-read cost into the next batch: chain
-                             // fill 265.6-265.8 us against 307.1-308.3 (profiles/r06/hint6)
+        // nontemporal field stores (round 6): the header lines they write carry no first-read
+        // cost into the next batch: chain fill 265.6-265.8 us against 307.1-308.3
+        // with plain stores (profiles/r06/hint6)
         if (fa) __builtin_nontemporal_store((uint16_t)bswap16(sums[i]), reinterpret_cast<u16_any_align *>(fa));
-#else
-        if (fa) *reinterpret_cast<u16_any_align *>(fa) = (uint16_t)bswap16(sums[i]);
-#endif
     }
 }
 
@@ -243,37 +237,21 @@ __device__ __forceinline__ uint32_t parity_below(uint64_t mask, uint32_t s) {  /
 
 // SU = 4 (the default since round 4) holds four more segment quads per lane than SU = 2 and
 // gets 4 waves per SIMD (at 5 it spilled 68 bytes per lane at 96 VGPRs); SU = 2 keeps 5.
-// Chain runs (round 6; A/B build switch AIPSTACK_CHAIN_RUNS): long chunks that lie back to
-// back read as one stream-prefix run, short ones by their own lanes. Bit-exact (the chain
-// tests), but slower on CHAIN: 261.0-261.5 us against 251.8-254.5 for the gathered stream
-// (profiles/r06/chain6): a 31 KiB run with 43 boundaries per group costs the stream prefixes'
-// per-window scan and boundary evaluation more than the gathered stream's owner lookup. Off.
-#ifndef AIPSTACK_CHAIN_RUNS
-#define AIPSTACK_CHAIN_RUNS 0
-#endif
-constexpr bool kChainRuns = AIPSTACK_CHAIN_RUNS != 0;
-// Chain column runs (round 6; COLS): as chain runs, but the run chunks -- every non-empty
-// chunk that is not a lone short one (the short_first rule: header nodes apart from the
-// payload), in table order -- are read as column runs of at most kChainColMax chunks each
+// Tried in round 6 and removed: chain runs (back-to-back long chunks as one stream-prefix run,
+// short ones by their own lanes): bit-exact but 261.0-261.5 us on CHAIN against 251.8-254.5
+// for the gathered stream (profiles/r06/chain6; docs/HISTORY.md, code last in b66da65).
+// Chain column runs (round 6; COLS): when the run chunks -- every non-empty chunk that is not
+// a lone short one (the short_first rule: header nodes apart from the payload), in table
+// order -- lie back to back, they are read as column runs of at most kChainColMax chunks each
 // (sum_column_chunk, capture form: no per-window scan, no owner lookup, no line read through
 // the L2-allocating path), and the lone short ones each by its own lane (their first two
 // segments loaded before the runs). Any other layout: the gathered stream below. The kernel
 // for AIPSTACK_CHKSUM_JUST_WRITTEN (launch_chain): on plain-written CHAIN 323.5 against the
 // gathered stream's 367.3 us; on bytes read before, 279-283 against 253-255 (more per-boundary
 // work at 45 segments per boundary, 4 waves per SIMD against 5), so not the default
-// (profiles/r06/ccols/). AIPSTACK_CHAIN_COLS=1: every launch (A/B build switch).
-#ifndef AIPSTACK_CHAIN_COLS
-#define AIPSTACK_CHAIN_COLS 0
-#endif
-constexpr bool kChainCols = AIPSTACK_CHAIN_COLS != 0;
-#ifndef AIPSTACK_CHAIN_COLS_MAXP
-#define AIPSTACK_CHAIN_COLS_MAXP 32
-#endif
-constexpr int kChainColMax = AIPSTACK_CHAIN_COLS_MAXP;  // run chunks per column run (16 or 32)
-#ifndef AIPSTACK_CHAIN_COLS_U
-#define AIPSTACK_CHAIN_COLS_U 6
-#endif
-constexpr int kChainColU = AIPSTACK_CHAIN_COLS_U;  // windows per group in those runs
+// (profiles/r06/ccols/).
+constexpr int kChainColMax = 32;  // run chunks per column run
+constexpr int kChainColU = 6;     // windows per group in those runs
 template <bool NT, int SU, bool COLS = false>
 __global__ __launch_bounds__(kBlock, SU > 2 ? 4 : 5) void chksum_chain_kernel(
     const uint64_t *__restrict__ chunk_addr, const uint32_t *__restrict__ chunk_len,
@@ -282,7 +260,7 @@ __global__ __launch_bounds__(kBlock, SU > 2 ? 4 : 5) void chksum_chain_kernel(
     uint32_t flags, uint32_t short_first) {
     __shared__ uint64_t lds_acc[kWavesPerBlock][kWave];  // per-chain sum of chunk sums
     __shared__ int lds_mark[kWavesPerBlock][kWave];      // chain starting at chunk lane
-    constexpr bool kCols = (COLS || kChainCols) && SU > 2;
+    constexpr bool kCols = COLS && SU > 2;
     // gathered stream owners (chain column runs: in the wave's column rows, which a slice that
     // takes the gathered stream does not use)
     __shared__ typename std::conditional<kCols, char, GatherLds[kWavesPerBlock]>::type lds_gather;
@@ -299,8 +277,10 @@ __global__ __launch_bounds__(kBlock, SU > 2 ? 4 : 5) void chksum_chain_kernel(
     const bool edge_nt = (flags & AIPSTACK_CHKSUM_JUST_WRITTEN) != 0;  // 
     uint64_t *acc = lds_acc[wave_in_block];
     int *mark = lds_mark[wave_in_block];
-    const uint32_t voff = (uint32_t)lane * 16u;  // (chain runs: this lane's segment in a window)
+    const uint32_t voff = (uint32_t)lane * 16u;  // (column runs: this lane's segment in a window)
     auto gather_lds = [&]() -> GatherLds * {
+        static_assert(sizeof(GatherLds) <= sizeof(ColRowsN<kChainColMax>),
+                      "the gathered stream's owners must fit in a wave's column rows");
         if constexpr (kCols)
             return reinterpret_cast<GatherLds *>(col_rows[wave_in_block]);
         else
@@ -371,43 +351,7 @@ __global__ __launch_bounds__(kBlock, SU > 2 ? 4 : 5) void chksum_chain_kernel(
             // 241.0-241.7 vs 241.9-242.9 us (profiles/r04/short, probe).
             uint32_t sums = 0;
             const uint32_t lv = valid ? l : 0u;
-            bool done = false;
-            if constexpr (kChainRuns && SU > 2) {  // (SU 2, 5 waves per SIMD: would spill)
-                // Chain runs (round 6): when the group's long chunks, in table order, lie back
-                // to back -- the payload pieces of consecutive segments cut from one send
-                // buffer, tcp/IpTcpProto_output.h:1251-1277 -- they are read as ONE run with
-                // stream prefixes (sum_stream_chunk, C's loader: no owner lookup, no 64-bit
-                // address per window) in lanes 0..nl-1, and the short ones (header nodes, at
-                // most short_first bytes) each by its own lane. Any other layout: the gathered
-                // stream below. Each chunk's sum returns to its lane through the inverse
-                // permutation, as there.
-                const bool shortc = short_first != 0u && lv != 0u && lv <= short_first;
-                const uint64_t lm = __builtin_amdgcn_ballot_w64(lv != 0u && !shortc);
-                const uint32_t nl = (uint32_t)__builtin_popcountll(lm);
-                const uint32_t below_l = __builtin_amdgcn_mbcnt_hi(
-                    (uint32_t)(lm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)lm, 0u));
-                const bool longc = ((lm >> lane) & 1ull) != 0;
-                const uint32_t rank = longc ? below_l : nl + (uint32_t)lane - below_l;
-                const int to = (int)(rank << 2);
-                const uint32_t a_lo = (uint32_t)__builtin_amdgcn_ds_permute(to, (int)(uint32_t)a);
-                const uint32_t a_hi = (uint32_t)__builtin_amdgcn_ds_permute(to, (int)(uint32_t)(a >> 32));
-                const uint32_t l_p = (uint32_t)__builtin_amdgcn_ds_permute(to, (int)lv);
-                const uint64_t a_p = ((uint64_t)a_hi << 32) | a_lo;
-                if (nl != 0u && stream_ok(a_p, a_p + l_p, lane, (int)nl)) {
-                    const uint32_t s_long = sum_stream_chunk<16, NT>(a_p, a_p + l_p, lane,
-                                                                     (int)nl, voff);
-                    // the short ones: lanes nl.. hold them (and the empty chunks, l_p = 0)
-                    const uint32_t nsg = ((uint32_t)lane >= nl && l_p)
-                                             ? (((uint32_t)a_p & 15u) + l_p + 15u) >> 4 : 0u;
-                    const uint32_t kmax = (uint32_t)__builtin_amdgcn_readlane(
-                        wave_max_scan((int)nsg), kWave - 1);
-                    const uint32_t s_short = sum_own_short_chunk(a_p, (uint32_t)lane >= nl ? l_p : 0u,
-                                                                 kmax);
-                    const uint32_t s_p = (uint32_t)lane < nl ? s_long : s_short;
-                    sums = (uint32_t)__builtin_amdgcn_ds_bpermute(to, (int)s_p);
-                    done = true;
-                }
-            }
+            bool done = false;  // summed as column runs (else: the gathered stream below)
             if constexpr (kCols) {
                 if (short_first != 0u) {
                     // lone short chunks (the short_first rule below), run chunks, empty ones
@@ -448,7 +392,11 @@ __global__ __launch_bounds__(kBlock, SU > 2 ? 4 : 5) void chksum_chain_kernel(
                         if (nsg > 0u) h0 = __builtin_nontemporal_load(hp);
                         if (nsg > 1u) h1 = __builtin_nontemporal_load(hp + 1);
                         uint32_t s_p = 0;
-                        // (cpk as a run-time value: the column differences' loop stays rolled)
+                        // (cpk as a run-time value: the column differences' loop stays rolled.
+                        // It equals kChainColMax, the size col_rows is declared with, only
+                        // because both public entry points, aipstack_chksum_batch_chain and
+                        // aipstack_chksum_batch_chain_fill, pass on named flag bits alone, so
+                        // bit 31 of `flags` is never set here.)
                         const uint32_t cpk = (uint32_t)kChainColMax | (flags & 0x80000000u);
                         for (uint32_t r0 = 0; r0 < nr; r0 += (uint32_t)kChainColMax) {
                             const int cnt_r = (int)min(nr - r0, (uint32_t)kChainColMax);
@@ -456,13 +404,8 @@ __global__ __launch_bounds__(kBlock, SU > 2 ? 4 : 5) void chksum_chain_kernel(
                             const uint64_t S = ((uint64_t)(uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)a_hi) << 32) |
                                                (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)a_lo);
                             const uint64_t E = S + (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)l_p);
-                            uint32_t sr;
-                            if (COLS || edge_nt)  // (the COLS kernel runs for the hint alone)
-                                sr = sum_column_chunk<NT, kChainColU, true, kChainColMax>(
-                                    S, E, lane, cnt_r, voff, cpk, col_rows[wave_in_block]);
-                            else
-                                sr = sum_column_chunk<NT, kChainColU, false, kChainColMax>(
-                                    S, E, lane, cnt_r, voff, cpk, col_rows[wave_in_block]);
+                            const uint32_t sr = sum_column_chunk<NT, kChainColU, true, kChainColMax>(
+                                S, E, lane, cnt_r, voff, cpk, col_rows[wave_in_block]);
                             const uint32_t back = (uint32_t)__builtin_amdgcn_ds_bpermute(
                                 (int)((((uint32_t)lane - r0) & 63u) << 2), (int)sr);
                             if ((uint32_t)lane >= r0 && (uint32_t)lane < r0 + (uint32_t)cnt_r)
@@ -476,35 +419,36 @@ __global__ __launch_bounds__(kBlock, SU > 2 ? 4 : 5) void chksum_chain_kernel(
                     }
                 }
             }
-            if (done) {
-            } else if (short_first) {
-                // a short chunk goes first only if it shares no line with its neighbours in
-                // the table (a header node apart from the payload; a short payload piece
-                // stays beside the pieces it shares lines with)
-                const uint32_t line_s = (uint32_t)(a >> 7);
-                const uint32_t line_e = (uint32_t)((a + lv - 1u) >> 7);
-                const uint32_t prev_e =
-                    (uint32_t)__builtin_amdgcn_ds_bpermute((lane - 1) << 2, (int)line_e);
-                const uint32_t next_s =
-                    (uint32_t)__builtin_amdgcn_ds_bpermute((lane + 1) << 2, (int)line_s);
-                const bool sc = lv != 0 && lv <= short_first && prev_e != line_s &&
-                                next_s != line_e;
-                const uint64_t sm = __builtin_amdgcn_ballot_w64(sc);
-                const uint32_t below_s = __builtin_amdgcn_mbcnt_hi(
-                    (uint32_t)(sm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)sm, 0u));
-                const uint32_t rank = sc ? below_s
-                                         : (uint32_t)__builtin_popcountll(sm) + (uint32_t)lane - below_s;
-                const int to = (int)(rank << 2);
-                const uint32_t a_lo = (uint32_t)__builtin_amdgcn_ds_permute(to, (int)(uint32_t)a);
-                const uint32_t a_hi = (uint32_t)__builtin_amdgcn_ds_permute(to, (int)(uint32_t)(a >> 32));
-                const uint32_t l_p = (uint32_t)__builtin_amdgcn_ds_permute(to, (int)lv);
-                const uint32_t s_p = sum_gathered_chunks<SU, NT>(
-                    ((uint64_t)a_hi << 32) | a_lo, l_p, lane, gather_lds(), nullptr,
-                    edge_nt);
-                sums = (uint32_t)__builtin_amdgcn_ds_bpermute(to, (int)s_p);
-            } else {
-                sums = sum_gathered_chunks<SU, NT>(a, lv, lane, gather_lds(),
-                                                   nullptr, edge_nt);
+            if (!done) {
+                if (short_first) {
+                    // a short chunk goes first only if it shares no line with its neighbours in
+                    // the table (a header node apart from the payload; a short payload piece
+                    // stays beside the pieces it shares lines with)
+                    const uint32_t line_s = (uint32_t)(a >> 7);
+                    const uint32_t line_e = (uint32_t)((a + lv - 1u) >> 7);
+                    const uint32_t prev_e =
+                        (uint32_t)__builtin_amdgcn_ds_bpermute((lane - 1) << 2, (int)line_e);
+                    const uint32_t next_s =
+                        (uint32_t)__builtin_amdgcn_ds_bpermute((lane + 1) << 2, (int)line_s);
+                    const bool sc = lv != 0 && lv <= short_first && prev_e != line_s &&
+                                    next_s != line_e;
+                    const uint64_t sm = __builtin_amdgcn_ballot_w64(sc);
+                    const uint32_t below_s = __builtin_amdgcn_mbcnt_hi(
+                        (uint32_t)(sm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)sm, 0u));
+                    const uint32_t rank = sc ? below_s
+                                             : (uint32_t)__builtin_popcountll(sm) + (uint32_t)lane - below_s;
+                    const int to = (int)(rank << 2);
+                    const uint32_t a_lo = (uint32_t)__builtin_amdgcn_ds_permute(to, (int)(uint32_t)a);
+                    const uint32_t a_hi = (uint32_t)__builtin_amdgcn_ds_permute(to, (int)(uint32_t)(a >> 32));
+                    const uint32_t l_p = (uint32_t)__builtin_amdgcn_ds_permute(to, (int)lv);
+                    const uint32_t s_p = sum_gathered_chunks<SU, NT>(
+                        ((uint64_t)a_hi << 32) | a_lo, l_p, lane, gather_lds(), nullptr,
+                        edge_nt);
+                    sums = (uint32_t)__builtin_amdgcn_ds_bpermute(to, (int)s_p);
+                } else {
+                    sums = sum_gathered_chunks<SU, NT>(a, lv, lane, gather_lds(),
+                                                       nullptr, edge_nt);
+                }
             }
             uint32_t r = fold16(sums);
             if ((uint32_t)(a & 1) == q)

@@ -32,17 +32,8 @@ constexpr int kHdrSegs = 8;
 constexpr int kHdrDwords = 23;  // frame bytes [0, 92) realigned to the frame start
 constexpr uint32_t kHdrNeed = 97;
 constexpr uint64_t kMaxSlotStride = AIPSTACK_CHKSUM_MAX_SLOT_STRIDE;
-// Records (the split fill's read pass, the records-only pass): nontemporal stores (1) or
-// ordinary ones (0), an A/B build switch.
-#ifndef AIPSTACK_FRAME_REC_NT
-#define AIPSTACK_FRAME_REC_NT 1
-#endif
 // The in-place Tx fills' field stores by default (tunable "tx_store", FieldSectors below).
-#ifndef AIPSTACK_TX_STORE_DEFAULT
-#define AIPSTACK_TX_STORE_DEFAULT 0
-#endif
-constexpr int kTxStoreDefault = AIPSTACK_TX_STORE_DEFAULT;
-
+constexpr int kTxStoreDefault = 0;
 
 __device__ __forceinline__ uint32_t bswap32(uint32_t x) {
     return __builtin_bswap32(x);
@@ -62,17 +53,9 @@ __device__ __forceinline__ uint32_t be16_at(uint32_t le_dword, int byte) {  // b
 // an odd address is one store instruction, not two byte stores (the frame fields sit at
 // S + 24 and S + fld, odd whenever the frame starts at an odd address).
 typedef uint16_t u16_any_align __attribute__((aligned(1)));
-#ifndef AIPSTACK_TX_STORE_MODE  // experiments only (tools/sweep.py --lib): 1 = nontemporal,
-#define AIPSTACK_TX_STORE_MODE 0   // 2 = no field stores (measures their cost; wrong output)
-#endif
+// A plain store: nontemporal field stores in the scatter pass lost in round 3 (docs/HISTORY.md).
 __device__ __forceinline__ void store_be16(uint64_t addr, uint32_t v) {
-#if AIPSTACK_TX_STORE_MODE == 0
     *reinterpret_cast<u16_any_align *>(addr) = (uint16_t)bswap16(v);
-#elif AIPSTACK_TX_STORE_MODE == 1
-    __builtin_nontemporal_store((uint16_t)bswap16(v), reinterpret_cast<u16_any_align *>(addr));
-#else
-    asm volatile("" ::"v"(v), "v"(addr));  // keep the value live, store nothing
-#endif
 }
 
 // Sector stores (round 4, the in-place Tx fills' `SECT` form). A 2-byte field store makes a
@@ -107,20 +90,10 @@ __device__ __forceinline__ uint32_t frame_w1(int fld, bool ip, bool l4, int stat
 }
 
 // The stores of one frame: its status byte, and for Tx the two checksum fields in place.
-#ifndef AIPSTACK_TX_RETOUCH  // experiment: load the field dwords again right before the stores
-#define AIPSTACK_TX_RETOUCH 0
-#endif
 template <bool TX>
 __device__ __forceinline__ void store_frame(uint64_t S, uint32_t w0, uint32_t w1,
                                             uint8_t *__restrict__ status, uint64_t i) {
     status[i] = (uint8_t)(w1 >> 16);
-    if constexpr (TX && AIPSTACK_TX_RETOUCH) {
-        typedef __attribute__((address_space(1))) const uint32_t gdw;
-        uint32_t t0 = 0, t1 = 0;
-        if (w1 & 0x100u) t0 = *(const gdw *)((S + 24) & ~(uint64_t)3);
-        if (w1 & 0x200u) t1 = *(const gdw *)((S + (w1 & 0xFFu)) & ~(uint64_t)3);
-        asm volatile("" ::"v"(t0), "v"(t1));
-    }
     if constexpr (TX) {
         if (w1 & 0x100u) store_be16(S + 24, w0);
         if (w1 & 0x200u) store_be16(S + (w1 & 0xFFu), w0 >> 16);
@@ -421,29 +394,24 @@ __device__ __forceinline__ uint32_t hdr_below(const u32x4 (&seg)[kHdrSegs],
 // 8 KiB held the kernel at 4 waves per SIMD by LDS alone).
 constexpr uint32_t kGatherWindows = 64;
 constexpr uint32_t kCaptureFrames = 32;
-#ifndef AIPSTACK_FRAME_NT  // experiments: 0 = the frame stream loads with the default policy
-#define AIPSTACK_FRAME_NT 1
-#endif
+constexpr bool kFrameNT = true;  // the frame stream loads nontemporal (every byte read once)
 constexpr uint32_t kHdrSlots = kCaptureFrames * kHdrSegs;  // at most 8 segments per frame
 
-// Round 5 (AIPSTACK_FRAME_HCAP): the capture also stores H at each captured segment's start,
-// so a frame's H(A0) is read from LDS after the stream instead of fetched per window with a
-// ds_bpermute (and its wait) as a stream boundary.
-#ifndef AIPSTACK_FRAME_HCAP
-#define AIPSTACK_FRAME_HCAP 1
-#endif
+// Round 5: the capture also stores H at each captured segment's start, so a frame's H(A0) is
+// read from LDS after the stream instead of fetched per window with a ds_bpermute (and its
+// wait) as a stream boundary.
 struct FrameLds {
     uint64_t wmask[kGatherWindows + 8];  // per window: the lanes holding header segments
                                          // (+8: whole groups past the last window read 0)
     u32x4 slots[kHdrSlots];          // the compact header segments
-    uint32_t hslot[AIPSTACK_FRAME_HCAP ? kHdrSlots : 1];  // H at each slot's segment start
+    uint32_t hslot[kHdrSlots];       // H at each slot's segment start
 };
 
 // Capture hook: group(w) fetches the group's U window masks into SGPRs (broadcast LDS
 // reads); window(v, w) writes the lanes of the mask to consecutive compact slots.
 template <int U>
 struct HeaderCapture {
-    static constexpr bool kWantH = AIPSTACK_FRAME_HCAP != 0;
+    static constexpr bool kWantH = true;
     const uint64_t *wmask;
     u32x4 *slots;
     uint32_t *hslot;
@@ -475,26 +443,16 @@ struct HeaderCapture {
         typedef __attribute__((address_space(3))) u32x4 lds_seg;
         const uint32_t addr = (uint32_t)(uintptr_t)(lds_seg *)(slots + count) + 16u * below;
         uint64_t save;
-        if constexpr (kWantH) {
-            typedef __attribute__((address_space(3))) uint32_t lds_h;
-            const uint32_t haddr = (uint32_t)(uintptr_t)(lds_h *)(hslot + count) + 4u * below;
-            asm volatile(
-                "s_and_saveexec_b64 %0, %2\n\t"
-                "ds_write_b128 %1, %3\n\t"
-                "ds_write_b32 %4, %5\n\t"
-                "s_mov_b64 exec, %0"
-                : "=&s"(save)
-                : "v"(addr), "s"(m), "v"(v), "v"(haddr), "v"(hv)
-                : "memory", "scc");
-        } else {
-            asm volatile(
-                "s_and_saveexec_b64 %0, %2\n\t"
-                "ds_write_b128 %1, %3\n\t"
-                "s_mov_b64 exec, %0"
-                : "=&s"(save)
-                : "v"(addr), "s"(m), "v"(v)
-                : "memory", "scc");
-        }
+        typedef __attribute__((address_space(3))) uint32_t lds_h;
+        const uint32_t haddr = (uint32_t)(uintptr_t)(lds_h *)(hslot + count) + 4u * below;
+        asm volatile(
+            "s_and_saveexec_b64 %0, %2\n\t"
+            "ds_write_b128 %1, %3\n\t"
+            "ds_write_b32 %4, %5\n\t"
+            "s_mov_b64 exec, %0"
+            : "=&s"(save)
+            : "v"(addr), "s"(m), "v"(v), "v"(haddr), "v"(hv)
+            : "memory", "scc");
         count += (uint32_t)__builtin_popcountll(m);
     }
 };
@@ -572,23 +530,15 @@ __device__ __forceinline__ FieldSectors pick_sectors(const u32x4 (&seg)[kHdrSegs
 // Stream mode (SU > 0, chunks whose frames lie back to back): (C) is replaced by stream
 // prefixes over the chunk's frames (chksum_device.h): each frame's L4 sum is
 // H(l4e) - H(l4s), minus the Tx checksum field's bytes; no per-frame loads or reductions.
-// Stream windows issued before the header parse (the rest after it): all of them hold
-// ~4 * SU more VGPRs through the parse.
-#ifndef AIPSTACK_FRAME_PREFETCH
-#define AIPSTACK_FRAME_PREFETCH(SU) ((SU) / 2)
-#endif
 // Frames whose headers are captured from the stream: the next group of windows issued before
 // the current one is summed (StreamRun's DB; round 4, profiles/r04/fdb: RX 120.1 -> 117.6 us,
 // split Tx fill 161.2 -> 155.8, records pass 129.2 -> 127.6; 128 VGPRs at 8 windows, no
-// spill, the same 4 waves per SIMD). A/B build switch: -DAIPSTACK_FRAME_DB=0.
-#ifndef AIPSTACK_FRAME_DB
-#define AIPSTACK_FRAME_DB 1
-#endif
+// spill, the same 4 waves per SIMD).
 // Ring slots: the L4 bytes past the header blocks read as one gathered stream of the chunk's
-// frames (1) or one frame per wave instruction pair (0, rounds 3-4), an A/B build switch.
-#ifndef AIPSTACK_FRAME_SLOT_GATHER
-#define AIPSTACK_FRAME_SLOT_GATHER 1
-#endif
+// frames (round 4; rounds 3-4 read one frame per wave instruction pair).
+// Long runs: stream windows issued before the header parse (the rest after it); all of them
+// would hold ~4 * SU more VGPRs through the parse.
+constexpr int frame_prefetch(int su) { return su / 2; }
 // GATHER: where the parse's header segments come from (launch_frames picks it):
 //   kHdrLoads    per-lane loads before the stream (default policy);
 //   kHdrCapture  copied out of the stream windows as they pass (Rx, the records-only pass);
@@ -690,7 +640,7 @@ __device__ __forceinline__ FrameOut process_chunk(const Desc &desc, uint64_t p0,
                 touch1 = __builtin_amdgcn_raw_buffer_load_b32(
                     hrsrc, act ? (fo + 50u) & ~3u : 0xFFFFFFF0u, 0u, 0);
             }
-            StreamRun<SU, NT, SU, AIPSTACK_FRAME_DB != 0> run;
+            StreamRun<SU, NT, SU, true> run;
             run.begin(base, X1, voff);
             // compact slot of r0: the union segments below it. Regions start and end in
             // lane order, so region j adds [max(r0_j, r1_{j-1}), r1_j) to the union.
@@ -705,13 +655,13 @@ __device__ __forceinline__ FrameOut process_chunk(const Desc &desc, uint64_t p0,
             cap.slots = lds->slots;
             cap.hslot = lds->hslot;
             cap.count = 0;
-            // (HCAP: no stream boundary but X1; H(A0) comes from the capture after the stream)
-            const uint64_t bs[1] = {act && !AIPSTACK_FRAME_HCAP ? A0 : X1};
+            // (no stream boundary but X1; H(A0) comes from the capture after the stream)
+            const uint64_t bs[1] = {X1};
             uint32_t hA[1], hx;
             run.template prefixes<1, true>(bs, hA, hx, voff, cap);
             __builtin_amdgcn_wave_barrier();
-            if constexpr (AIPSTACK_FRAME_HCAP)  // r0 < nseg: its segment was captured at cslot
-                hA[0] = act && nmine ? lds->hslot[min(cslot, kHdrSlots - 1u)] : hx;
+            // r0 < nseg: its segment was captured at cslot
+            hA[0] = act && nmine ? lds->hslot[min(cslot, kHdrSlots - 1u)] : hx;
             // this lane's header blocks, and the next frame's first block (its start)
 #pragma unroll
             for (int i = 0; i < kHdrSegs; ++i) {
@@ -762,7 +712,7 @@ __device__ __forceinline__ FrameOut process_chunk(const Desc &desc, uint64_t p0,
             // and arrive during the parse.
             load_headers();
             have_headers = true;
-            StreamRun<SU, NT, AIPSTACK_FRAME_PREFETCH(SU)> run;
+            StreamRun<SU, NT, frame_prefetch(SU)> run;
             run.begin(base, X1, voff);
             fl = parse_lane<TX, true>(seg, S, len, hb_end);
             // (no sector stores here: their 16 VGPRs would live through the stream)
@@ -816,7 +766,7 @@ __device__ __forceinline__ FrameOut process_chunk(const Desc &desc, uint64_t p0,
         // are not back to back (16 more VGPRs through the per-frame loop)
         if constexpr (SECT && !Desc::kStream) fsec = pick_sectors(seg, S, E, fl);
         uint32_t sums;
-        if constexpr (!Desc::kStream && AIPSTACK_FRAME_SLOT_GATHER && Desc::kEdge) {
+        if constexpr (!Desc::kStream && Desc::kEdge) {
             // (C) ring slots: the remaining L4 bytes of the chunk's frames as one gathered
             // stream of just their segments (chksum_device.h; round 4)
             const uint32_t l4rest = lane < cnt ? (uint32_t)(fl.ce - fl.cs) : 0u;
@@ -826,7 +776,7 @@ __device__ __forceinline__ FrameOut process_chunk(const Desc &desc, uint64_t p0,
             const LaneMeta meta = lane_meta(fl.cs, fl.ce);
             // (C) the remaining L4 bytes, one frame per wave, P frames' loads in flight
             NoMaskHook hook;
-            sums = sum_lane_packets<U, P, AIPSTACK_ROWS_FRAMES, NT>(
+            sums = sum_lane_packets<U, P, NT>(
                 meta, __builtin_amdgcn_ballot_w64(need), lane, voff, not_lane0, hook);
         }
         // both parts (< 2^24 + 2^17), folded
@@ -899,15 +849,9 @@ __device__ __forceinline__ void store_frame_lines(const FrameOut &o, uint32_t fl
 // The classic kernel: a wave walks its chunks and stores each chunk's results right after
 // it. SPLIT (Tx only): lane j writes frame j's record (w0 | w1 << 32) to a workspace
 // instead, and tx_scatter_kernel stores the fields after the whole read pass.
-#ifndef AIPSTACK_FRAME_WAVES_PER_SIMD  // occupancy the register budget is fitted to
-#define AIPSTACK_FRAME_WAVES_PER_SIMD 4
-#endif
-#ifndef AIPSTACK_FRAME_RX_WAVES_PER_SIMD  // the same for Rx verify (no field stores)
-#define AIPSTACK_FRAME_RX_WAVES_PER_SIMD AIPSTACK_FRAME_WAVES_PER_SIMD
-#endif
+constexpr int kFrameWavesPerSimd = 4;  // occupancy the register budget is fitted to (Tx and Rx)
 template <class Desc, bool TX, int U, int P, bool NT, int SU, bool SPLIT, int GATHER, int STORE>
-__global__ __launch_bounds__(kBlock, TX ? AIPSTACK_FRAME_WAVES_PER_SIMD
-                                        : AIPSTACK_FRAME_RX_WAVES_PER_SIMD) void frame_kernel(Desc desc, uint64_t n,
+__global__ __launch_bounds__(kBlock, kFrameWavesPerSimd) void frame_kernel(Desc desc, uint64_t n,
                                                        uint32_t chunks_per_wave,
                                                        uint32_t chunk_packets,
                                                        uint8_t *__restrict__ status,
@@ -924,7 +868,7 @@ __global__ __launch_bounds__(kBlock, TX ? AIPSTACK_FRAME_WAVES_PER_SIMD
     constexpr bool kGather = SU > 0 && GATHER != kHdrLoads;
     __shared__ FrameLds lds[kGather ? kWavesPerBlock : 1];  // 9 KiB per wave (gathered stream)
     FrameLds *my = &lds[kGather ? wave_in_block : 0];
-    constexpr bool kSlotGather = !Desc::kStream && AIPSTACK_FRAME_SLOT_GATHER && Desc::kEdge;
+    constexpr bool kSlotGather = !Desc::kStream && Desc::kEdge;
     __shared__ GatherLds glds[kSlotGather ? kWavesPerBlock : 1];  // ring slots' L4 stream
     GatherLds *mg = &glds[kSlotGather ? wave_in_block : 0];
     constexpr bool kLines = STORE == kTxStoreLines;  // ring slots only (launch_frames_slotted_d)
@@ -942,18 +886,12 @@ __global__ __launch_bounds__(kBlock, TX ? AIPSTACK_FRAME_WAVES_PER_SIMD
                               p0 + lane);
         } else if (lane < cnt) {
             if constexpr (SPLIT)
-#if AIPSTACK_EXP_NO_RECORDS  // experiment: price of the record stores (wrong output)
-                asm volatile("" ::"v"(o.w0), "v"(o.w1));
-#elif AIPSTACK_FRAME_REC_NT
                 // nontemporal (round 6): the records pass 126.5-130.9 us against 128.3-130.3
-                // (profiles/r06/recnt), its probe 127.7 against 130.1; and a reader of the
-                // records (the scatter pass, a D2H copy) then finds no freshly written lines
-                // 
+                // with ordinary stores (profiles/r06/recnt), its probe 127.7 against 130.1; and
+                // a reader of the records (the scatter pass, a D2H copy) then finds no freshly
+                // written lines
                 __builtin_nontemporal_store((uint64_t)o.w0 | (uint64_t)o.w1 << 32,
                                             records + p0 + lane);
-#else
-                records[p0 + lane] = (uint64_t)o.w0 | (uint64_t)o.w1 << 32;
-#endif
             else if constexpr (STORE == kTxStoreSectors)
                 store_frame_sectors(o.S, o.w0, o.w1, o.fs, status, p0 + lane);
             else
@@ -992,7 +930,7 @@ int launch_frames_g(const Desc &desc, uint64_t n, uint8_t *d_status, uint64_t *d
     const uint64_t blocks = (waves + kWavesPerBlock - 1) / kWavesPerBlock;
     if (blocks > 0x7FFFFFFFull || cpw > 0xFFFFFFFFull) return AIPSTACK_CHKSUM_EINVAL;
 #define AIPSTACK_LAUNCH_FRAMES(P, SU)                                                          \
-    hipLaunchKernelGGL((frame_kernel<Desc, TX, 2, P, AIPSTACK_FRAME_NT != 0, SU, SPLIT, GATHER,  \
+    hipLaunchKernelGGL((frame_kernel<Desc, TX, 2, P, kFrameNT, SU, SPLIT, GATHER,             \
                                      STORE>),                                                    \
                        dim3((unsigned)blocks), dim3(kBlock), tuning_lds_pad(0), stream, desc, n, \
                        (uint32_t)cpw,                                                           \
