@@ -300,6 +300,18 @@ def _out_tensor(out, n: int, like):
     return out
 
 
+def _records_out(out, n: int, frames):
+    """The 64-bit device tensor the Tx records go to: the caller's, checked, or a new one."""
+    if out is None:
+        torch = _torch()
+        return torch.empty(n, dtype=torch.int64, device=frames.device)
+    _require_device(out, "out")
+    if out.element_size() != 8 or out.numel() < n:
+        raise ValueError("out must be a 64-bit device tensor with >= n elements")
+    _same_device(out, frames, "out and frames")
+    return out
+
+
 def chksum_batch_strided(buf, stride: int, length: int, n: int, *, out=None,
                          final: bool = False, byte_offset: int = 0, stream=None,
                          just_written: bool = False):
@@ -398,11 +410,9 @@ def tx_fill_slotted(frames, slot_stride: int, lens, *, out=None, stream=None, sp
 
 def tx_fill_records_slotted(frames, slot_stride: int, lens, *, out=None, stream=None):
     """The Tx records (see :func:`tx_fill_records`) of a ring of frame slots."""
-    torch = _torch()
     _require_device(frames, "frames")
     n = _require_lens(lens, frames.numel() * frames.element_size(), slot_stride, frames)
-    if out is None:
-        out = torch.empty(n, dtype=torch.int64, device=frames.device)
+    out = _records_out(out, n, frames)
     _check(_lib.load().aipstack_chksum_tx_fill_records_slotted(
         frames.data_ptr(), slot_stride, lens.data_ptr(), n, out.data_ptr(),
         _stream_handle(stream, frames)), "aipstack_chksum_tx_fill_records_slotted")
@@ -430,560 +440,9 @@ def chksum_batch_seeded_csr(buf, offsets, states, *, out=None, stream=None):
     return out
 
 
-def _host_u64(a):
-    """Host offsets as the C-ABI's uint64: a contiguous int64 array is passed as it is (a
-    view; the engine rejects the huge values a negative entry becomes, as non-decreasing
-    offsets within the frames), anything else is converted (a copy)."""
-    if isinstance(a, np.ndarray) and a.dtype == np.int64 and a.flags.c_contiguous:
-        return a.view(np.uint64)
-    return np.ascontiguousarray(a, dtype=np.uint64)
-
-
-def _host_u32(a):
-    """Host lengths as the C-ABI's uint32 (int32 viewed, as _host_u64; the engine rejects
-    lengths above the slot stride)."""
-    if isinstance(a, np.ndarray) and a.dtype == np.int32 and a.flags.c_contiguous:
-        return a.view(np.uint32)
-    return np.ascontiguousarray(a, dtype=np.uint32)
-
-
-class ChksumEngine:
-    """Host-memory streaming engine (C-ABI ``aipstack_chksum_engine_*``): checksums
-    batches held in HOST memory (numpy arrays) and returns results in host memory,
-    pipelining H2D / kernel / D2H over ``nstreams`` HIP streams. ``strided`` / ``csr`` are
-    synchronous; ``submit_strided`` / ``submit_csr`` return a ticket at once and
-    ``poll`` / ``wait`` complete it, so the caller can prepare its next batch meanwhile."""
-
-    def __init__(self, device: int = 0, chunk_bytes: int = 0, nstreams: int = 2):
-        self._lib = _lib.load()
-        h = ctypes.c_void_p()
-        _check(self._lib.aipstack_chksum_engine_create(device, chunk_bytes, nstreams,
-                                                       ctypes.byref(h)),
-               "aipstack_chksum_engine_create")
-        self._h = h
-        self._registered = []
-        self._inflight = {}
-
-    def close(self) -> None:
-        if self._h:
-            self._lib.aipstack_chksum_engine_destroy(self._h)  # waits for every stream
-            self._h = None
-            self._registered = []
-            self._inflight = {}
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def register(self, arr: np.ndarray) -> None:
-        """Page-lock `arr` (kept alive by the engine) so that the kernels read batches in it
-        where they lie (zero copy; or DMA'd directly with tune("engine_zero_copy", 0))."""
-        _check(self._lib.aipstack_chksum_engine_register(self._h, arr.ctypes.data, arr.nbytes),
-               "aipstack_chksum_engine_register")
-        self._registered.append(arr)
-
-    def unregister(self, arr: np.ndarray) -> None:
-        """Unpin `arr`; batches still in flight are completed first (C engine)."""
-        _check(self._lib.aipstack_chksum_engine_unregister(self._h, arr.ctypes.data),
-               "aipstack_chksum_engine_unregister")
-        self._registered = [a for a in self._registered if a is not arr]
-
-    @staticmethod
-    def _host_args(buf: np.ndarray, out, n: int, dtype=np.uint16) -> np.ndarray:
-        if not isinstance(buf, np.ndarray) or not buf.flags.c_contiguous:
-            raise ValueError("buf must be a C-contiguous numpy array")
-        if out is None:
-            return np.empty(max(n, 0), dtype=dtype)
-        if (not isinstance(out, np.ndarray) or out.dtype != dtype
-                or not out.flags.c_contiguous or not out.flags.writeable or out.size < n):
-            raise ValueError(f"out must be a writable C-contiguous {np.dtype(dtype).name} array "
-                             "of >= n elements")
-        return out
-
-    def strided(self, buf: np.ndarray, stride: int, length: int, n: int, *, out=None,
-                final: bool = False) -> np.ndarray:
-        if n and (n - 1) * stride + length > buf.nbytes:
-            raise ValueError("batch exceeds buf")
-        out = self._host_args(buf, out, n)
-        _check(self._lib.aipstack_chksum_engine_host_strided(
-            self._h, buf.ctypes.data, stride, length, n, out.ctypes.data,
-            AIPSTACK_CHKSUM_FINAL if final else 0), "aipstack_chksum_engine_host_strided")
-        return out
-
-    # ---- asynchronous batches: submit returns a ticket, poll / wait complete it --------
-
-    def submit_strided(self, buf: np.ndarray, stride: int, length: int, n: int, *, out=None,
-                       final: bool = False):
-        """Enqueue a strided batch; returns (ticket, out). `out` is filled when the batch
-        completes (wait / poll); a registered `buf` must not change until then."""
-        if n and (n - 1) * stride + length > buf.nbytes:
-            raise ValueError("batch exceeds buf")
-        out = self._host_args(buf, out, n)
-        t = ctypes.c_uint64(0)
-        st = self._lib.aipstack_chksum_engine_submit_strided(
-            self._h, buf.ctypes.data, stride, length, n, out.ctypes.data,
-            AIPSTACK_CHKSUM_FINAL if final else 0, ctypes.byref(t))
-        self._submitted(st, t.value, "aipstack_chksum_engine_submit_strided", buf, out)
-        return t.value, out
-
-    def submit_csr(self, buf: np.ndarray, offsets: np.ndarray, *, out=None,
-                   final: bool = False):
-        """Enqueue a CSR batch; returns (ticket, out) (see submit_strided)."""
-        o = _host_u64(offsets)
-        n = o.size - 1
-        if n > 0 and int(o[-1]) > buf.nbytes:
-            raise ValueError("offsets exceed buf")
-        out = self._host_args(buf, out, n)
-        t = ctypes.c_uint64(0)
-        st = self._lib.aipstack_chksum_engine_submit_csr(
-            self._h, buf.ctypes.data, o.ctypes.data, max(n, 0), out.ctypes.data,
-            AIPSTACK_CHKSUM_FINAL if final else 0, ctypes.byref(t))
-        self._submitted(st, t.value, "aipstack_chksum_engine_submit_csr", buf, o, out)
-        return t.value, out
-
-    def _keep(self, ticket, *arrays):
-        # the buffers the GPU and the completion still use stay alive until completion
-        if ticket:
-            self._inflight[ticket] = arrays
-
-    def _submitted(self, st, ticket, where, *arrays):
-        """After a submit_* C call: keep the arrays of a batch in flight, or, if the submit
-        failed part-way, complete the pieces it did enqueue (they still read `arrays` and,
-        for Tx, write into the frames) before raising."""
-        if st != AIPSTACK_CHKSUM_OK:
-            if ticket:
-                self._lib.aipstack_chksum_engine_wait(self._h, ticket)
-            raise ChksumError(st, where)
-        self._keep(ticket, *arrays)
-
-    def locality(self):
-        """(NUMA node of the device or -1, CPUs the engine's host threads are pinned to)."""
-        node, cpus = ctypes.c_int(-1), ctypes.c_int(0)
-        _check(self._lib.aipstack_chksum_engine_locality(self._h, ctypes.byref(node),
-                                                         ctypes.byref(cpus)),
-               "aipstack_chksum_engine_locality")
-        return node.value, cpus.value
-
-    def poll(self, ticket: int) -> bool:
-        """True once batch `ticket` is complete (its `out` filled); False while running."""
-        st = self._lib.aipstack_chksum_engine_poll(self._h, ticket)
-        if st == 1:
-            return False
-        self._inflight.pop(ticket, None)
-        _check(st, "aipstack_chksum_engine_poll")
-        return True
-
-    def wait(self, ticket: int) -> None:
-        """Block until batch `ticket` is complete."""
-        st = self._lib.aipstack_chksum_engine_wait(self._h, ticket)
-        self._inflight.pop(ticket, None)
-        _check(st, "aipstack_chksum_engine_wait")
-
-    def rx_verify(self, frames: np.ndarray, offsets: np.ndarray, *, out=None) -> np.ndarray:
-        """Rx verify of raw Ethernet frames in HOST memory (frame i =
-        ``frames[offsets[i]:offsets[i+1]]``): one AIPSTACK_RX_* verdict per frame (uint8),
-        as :func:`rx_verify` on the device."""
-        o = _host_u64(offsets)
-        n = o.size - 1
-        if n > 0 and int(o[-1]) > frames.nbytes:
-            raise ValueError("offsets exceed frames")
-        out = self._host_args(frames, out, n, np.uint8)
-        _check(self._lib.aipstack_chksum_engine_host_rx_verify(
-            self._h, frames.ctypes.data, o.ctypes.data, max(n, 0), out.ctypes.data),
-            "aipstack_chksum_engine_host_rx_verify")
-        return out
-
-    def submit_rx_verify(self, frames: np.ndarray, offsets: np.ndarray, *, out=None):
-        """Enqueue an Rx verify batch; returns (ticket, out) (see submit_strided)."""
-        o = _host_u64(offsets)
-        n = o.size - 1
-        if n > 0 and int(o[-1]) > frames.nbytes:
-            raise ValueError("offsets exceed frames")
-        out = self._host_args(frames, out, n, np.uint8)
-        t = ctypes.c_uint64(0)
-        st = self._lib.aipstack_chksum_engine_submit_rx_verify(
-            self._h, frames.ctypes.data, o.ctypes.data, max(n, 0), out.ctypes.data,
-            ctypes.byref(t))
-        self._submitted(st, t.value, "aipstack_chksum_engine_submit_rx_verify", frames, o, out)
-        return t.value, out
-
-    @staticmethod
-    def _tx_args(frames, offsets, status):
-        if not isinstance(frames, np.ndarray) or not frames.flags.writeable:
-            raise ValueError("frames must be a writable numpy array (filled in place)")
-        o = _host_u64(offsets)
-        n = o.size - 1
-        if n > 0 and int(o[-1]) > frames.nbytes:
-            raise ValueError("offsets exceed frames")
-        return o, n, ChksumEngine._host_args(frames, status, n, np.uint8)
-
-    def tx_fill(self, frames: np.ndarray, offsets: np.ndarray, *, status=None) -> np.ndarray:
-        """Tx fill of raw Ethernet frames in HOST memory, IN PLACE (frame i =
-        ``frames[offsets[i]:offsets[i+1]]``): the IPv4 header and L4 checksum fields are
-        written as :func:`tx_fill` does on the device; returns the per-frame AIPSTACK_TX_*
-        statuses (uint8)."""
-        o, n, status = self._tx_args(frames, offsets, status)
-        _check(self._lib.aipstack_chksum_engine_host_tx_fill(
-            self._h, frames.ctypes.data, o.ctypes.data, max(n, 0), status.ctypes.data),
-            "aipstack_chksum_engine_host_tx_fill")
-        return status
-
-    def submit_tx_fill(self, frames: np.ndarray, offsets: np.ndarray, *, status=None):
-        """Enqueue a Tx fill batch; returns (ticket, status). The frames are filled and
-        `status` written when the batch completes (wait / poll); `frames` must not be
-        touched until then."""
-        o, n, status = self._tx_args(frames, offsets, status)
-        # the completion reads the offsets again (it writes the fields into the frames, on
-        # the engine's applier thread): a private copy, so the caller may reuse its array
-        o = o.copy()
-        t = ctypes.c_uint64(0)
-        st = self._lib.aipstack_chksum_engine_submit_tx_fill(
-            self._h, frames.ctypes.data, o.ctypes.data, max(n, 0), status.ctypes.data,
-            ctypes.byref(t))
-        # the completion reads the offsets again (it writes the fields into the frames)
-        self._submitted(st, t.value, "aipstack_chksum_engine_submit_tx_fill", frames, o, status)
-        return t.value, status
-
-    # ---- ring slots: frame i = the lens[i] bytes at buf[i * slot_stride:] ----------------
-
-    @staticmethod
-    def _slot_args(buf, slot_stride: int, lens):
-        ln = _host_u32(lens)
-        n = ln.size
-        if slot_stride <= 0 or n * slot_stride > buf.nbytes:
-            raise ValueError("the buffer must hold n whole slots of slot_stride bytes")
-        return ln, n
-
-    def slotted(self, buf: np.ndarray, slot_stride: int, lens, *, out=None,
-                final: bool = False) -> np.ndarray:
-        """Checksums of the packets of a ring of slots in HOST memory
-        (``aipstack_chksum_engine_host_slotted``)."""
-        ln, n = self._slot_args(buf, slot_stride, lens)
-        out = self._host_args(buf, out, n)
-        _check(self._lib.aipstack_chksum_engine_host_slotted(
-            self._h, buf.ctypes.data, slot_stride, ln.ctypes.data, n, out.ctypes.data,
-            AIPSTACK_CHKSUM_FINAL if final else 0), "aipstack_chksum_engine_host_slotted")
-        return out
-
-    def submit_slotted(self, buf: np.ndarray, slot_stride: int, lens, *, out=None,
-                       final: bool = False):
-        ln, n = self._slot_args(buf, slot_stride, lens)
-        out = self._host_args(buf, out, n)
-        t = ctypes.c_uint64(0)
-        st = self._lib.aipstack_chksum_engine_submit_slotted(
-            self._h, buf.ctypes.data, slot_stride, ln.ctypes.data, n, out.ctypes.data,
-            AIPSTACK_CHKSUM_FINAL if final else 0, ctypes.byref(t))
-        self._submitted(st, t.value, "aipstack_chksum_engine_submit_slotted", buf, ln, out)
-        return t.value, out
-
-    def rx_verify_slotted(self, frames: np.ndarray, slot_stride: int, lens, *,
-                          out=None) -> np.ndarray:
-        """Rx verify of a ring of frame slots in HOST memory."""
-        ln, n = self._slot_args(frames, slot_stride, lens)
-        out = self._host_args(frames, out, n, np.uint8)
-        _check(self._lib.aipstack_chksum_engine_host_rx_verify_slotted(
-            self._h, frames.ctypes.data, slot_stride, ln.ctypes.data, n, out.ctypes.data),
-            "aipstack_chksum_engine_host_rx_verify_slotted")
-        return out
-
-    def submit_rx_verify_slotted(self, frames: np.ndarray, slot_stride: int, lens, *,
-                                 out=None):
-        """Enqueue an Rx verify batch of frame slots; returns (ticket, out). The slots must
-        not be refilled until the ticket completes (the receive loop of a TAP ring:
-        tap/linux/TapDeviceLinux.cpp:156-178)."""
-        ln, n = self._slot_args(frames, slot_stride, lens)
-        out = self._host_args(frames, out, n, np.uint8)
-        t = ctypes.c_uint64(0)
-        st = self._lib.aipstack_chksum_engine_submit_rx_verify_slotted(
-            self._h, frames.ctypes.data, slot_stride, ln.ctypes.data, n, out.ctypes.data,
-            ctypes.byref(t))
-        self._submitted(st, t.value, "aipstack_chksum_engine_submit_rx_verify_slotted", frames,
-                        ln, out)
-        return t.value, out
-
-    def submit_tx_fill_slotted(self, frames: np.ndarray, slot_stride: int, lens, *,
-                               status=None):
-        """Enqueue a Tx fill of frame slots, in place; returns (ticket, status). The frames
-        are filled when the ticket completes and must not be touched until then."""
-        if not frames.flags.writeable:
-            raise ValueError("frames must be writable (filled in place)")
-        ln, n = self._slot_args(frames, slot_stride, lens)
-        status = self._host_args(frames, status, n, np.uint8)
-        t = ctypes.c_uint64(0)
-        st = self._lib.aipstack_chksum_engine_submit_tx_fill_slotted(
-            self._h, frames.ctypes.data, slot_stride, ln.ctypes.data, n, status.ctypes.data,
-            ctypes.byref(t))
-        self._submitted(st, t.value, "aipstack_chksum_engine_submit_tx_fill_slotted", frames,
-                        ln, status)
-        return t.value, status
-
-    def tx_fill_slotted(self, frames: np.ndarray, slot_stride: int, lens, *,
-                        status=None) -> np.ndarray:
-        """Tx fill, in place, of a ring of frame slots in HOST memory."""
-        if not frames.flags.writeable:
-            raise ValueError("frames must be writable (filled in place)")
-        ln, n = self._slot_args(frames, slot_stride, lens)
-        status = self._host_args(frames, status, n, np.uint8)
-        _check(self._lib.aipstack_chksum_engine_host_tx_fill_slotted(
-            self._h, frames.ctypes.data, slot_stride, ln.ctypes.data, n, status.ctypes.data),
-            "aipstack_chksum_engine_host_tx_fill_slotted")
-        return status
-
-    def csr(self, buf: np.ndarray, offsets: np.ndarray, *, out=None,
-            final: bool = False) -> np.ndarray:
-        o = _host_u64(offsets)
-        n = o.size - 1
-        if n > 0 and int(o[-1]) > buf.nbytes:
-            raise ValueError("offsets exceed buf")
-        out = self._host_args(buf, out, n)
-        _check(self._lib.aipstack_chksum_engine_host_csr(
-            self._h, buf.ctypes.data, o.ctypes.data, n, out.ctypes.data,
-            AIPSTACK_CHKSUM_FINAL if final else 0), "aipstack_chksum_engine_host_csr")
-        return out
-
-
-class ChksumEngineGroup:
-    """Several devices behind one host-memory batch in ONE process (C-ABI
-    ``aipstack_chksum_engine_group_*``): one engine per entry of ``devices`` (repeats
-    allowed), each batch split into contiguous ranges of about equal bytes run concurrently
-    (small batches go whole to one device, round robin). The synchronous calls return the
-    results; ``submit_*`` return ``(ticket, out)`` at once, ``poll`` / ``wait`` complete a
-    ticket. ``last_status`` holds each engine's status of the last completed call."""
-
-    def __init__(self, devices, chunk_bytes: int = 0, nstreams: int = 4):
-        self._lib = _lib.load()
-        devs = (ctypes.c_int * len(devices))(*[int(d) for d in devices])
-        h = ctypes.c_void_p()
-        _check(self._lib.aipstack_chksum_engine_group_create(devs, len(devices), chunk_bytes,
-                                                             nstreams, ctypes.byref(h)),
-               "aipstack_chksum_engine_group_create")
-        self._h = h
-        self.size = len(devices)
-        self._registered = []
-        self._inflight = {}
-        self.last_status = [0] * self.size
-
-    def close(self) -> None:
-        if self._h:
-            self._lib.aipstack_chksum_engine_group_destroy(self._h)  # completes every batch
-            self._h = None
-            self._registered = []
-            self._inflight = {}
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def register(self, arr: np.ndarray) -> None:
-        _check(self._lib.aipstack_chksum_engine_group_register(self._h, arr.ctypes.data,
-                                                               arr.nbytes),
-               "aipstack_chksum_engine_group_register")
-        self._registered.append(arr)
-
-    def unregister(self, arr: np.ndarray) -> None:
-        _check(self._lib.aipstack_chksum_engine_group_unregister(self._h, arr.ctypes.data),
-               "aipstack_chksum_engine_group_unregister")
-        self._registered = [a for a in self._registered if a is not arr]
-
-    def _call(self, fn, where, *args):
-        ds = (ctypes.c_int * self.size)()
-        st = getattr(self._lib, fn)(self._h, *args, ds)
-        self.last_status = list(ds)
-        _check(st, where)
-
-    def _submit(self, fn, arrays, *args):
-        """A submit_* C call; the arrays of the batch stay referenced until it completes."""
-        t = ctypes.c_uint64(0)
-        st = getattr(self._lib, fn)(self._h, *args, ctypes.byref(t))
-        if st != AIPSTACK_CHKSUM_OK:
-            if t.value:  # ranges already enqueued still read (and, Tx, write) the arrays
-                self._lib.aipstack_chksum_engine_group_wait(self._h, t.value, None)
-            raise ChksumError(st, fn)
-        self._inflight[t.value] = arrays
-        return t.value
-
-    def poll(self, ticket: int) -> bool:
-        """True once group batch `ticket` is complete; False while a device still works."""
-        ds = (ctypes.c_int * self.size)()
-        st = self._lib.aipstack_chksum_engine_group_poll(self._h, ticket, ds)
-        if st == 1:
-            return False
-        self._inflight.pop(ticket, None)
-        self.last_status = list(ds)
-        _check(st, "aipstack_chksum_engine_group_poll")
-        return True
-
-    def wait(self, ticket: int) -> None:
-        """Block until group batch `ticket` is complete."""
-        ds = (ctypes.c_int * self.size)()
-        st = self._lib.aipstack_chksum_engine_group_wait(self._h, ticket, ds)
-        self._inflight.pop(ticket, None)
-        self.last_status = list(ds)
-        _check(st, "aipstack_chksum_engine_group_wait")
-
-    def locality(self):
-        """Per engine: (NUMA node of its device or -1, CPUs its host threads are pinned to)."""
-        out = []
-        for k in range(self.size):
-            e = self._lib.aipstack_chksum_engine_group_engine(self._h, k)
-            node, cpus = ctypes.c_int(-1), ctypes.c_int(0)
-            _check(self._lib.aipstack_chksum_engine_locality(e, ctypes.byref(node),
-                                                             ctypes.byref(cpus)),
-                   "aipstack_chksum_engine_locality")
-            out.append((node.value, cpus.value))
-        return out
-
-    def region_mapped(self, arr: np.ndarray) -> bool:
-        """Whether every device's kernels read the registered `arr` in place (zero copy)."""
-        st = self._lib.aipstack_chksum_engine_group_region_mapped(self._h, arr.ctypes.data)
-        _check(min(st, 0), "aipstack_chksum_engine_group_region_mapped")
-        return st == 1
-
-    def submit_strided(self, buf, stride: int, length: int, n: int, *, out=None, final=False):
-        if n and (n - 1) * stride + length > buf.nbytes:
-            raise ValueError("batch exceeds buf")
-        out = ChksumEngine._host_args(buf, out, n)
-        t = self._submit("aipstack_chksum_engine_group_submit_strided", (buf, out),
-                         buf.ctypes.data, stride, length, n, out.ctypes.data,
-                         AIPSTACK_CHKSUM_FINAL if final else 0)
-        return t, out
-
-    def submit_csr(self, buf, offsets, *, out=None, final=False):
-        # a copy: a range may be submitted later on its device's worker thread, after this
-        # returns, and must not see the caller refill its offsets (the bounds checked here)
-        o = _host_u64(offsets).copy()
-        n = o.size - 1
-        if n > 0 and int(o[-1]) > buf.nbytes:
-            raise ValueError("offsets exceed buf")
-        out = ChksumEngine._host_args(buf, out, n)
-        t = self._submit("aipstack_chksum_engine_group_submit_csr", (buf, o, out),
-                         buf.ctypes.data, o.ctypes.data, max(n, 0), out.ctypes.data,
-                         AIPSTACK_CHKSUM_FINAL if final else 0)
-        return t, out
-
-    def submit_rx_verify(self, frames, offsets, *, out=None):
-        o = _host_u64(offsets).copy()  # (as submit_csr)
-        n = o.size - 1
-        if n > 0 and int(o[-1]) > frames.nbytes:
-            raise ValueError("offsets exceed frames")
-        out = ChksumEngine._host_args(frames, out, n, np.uint8)
-        t = self._submit("aipstack_chksum_engine_group_submit_rx_verify", (frames, o, out),
-                         frames.ctypes.data, o.ctypes.data, max(n, 0), out.ctypes.data)
-        return t, out
-
-    def submit_tx_fill(self, frames, offsets, *, status=None):
-        o, n, status = ChksumEngine._tx_args(frames, offsets, status)
-        o = o.copy()  # read again when the fields are applied (see ChksumEngine.submit_tx_fill)
-        t = self._submit("aipstack_chksum_engine_group_submit_tx_fill", (frames, o, status),
-                         frames.ctypes.data, o.ctypes.data, max(n, 0), status.ctypes.data)
-        return t, status
-
-    def submit_slotted(self, buf, slot_stride: int, lens, *, out=None, final=False):
-        ln, n = ChksumEngine._slot_args(buf, slot_stride, lens)
-        ln = ln.copy()  # (as submit_csr: the lengths are read again on a worker thread)
-        out = ChksumEngine._host_args(buf, out, n)
-        t = self._submit("aipstack_chksum_engine_group_submit_slotted", (buf, ln, out),
-                         buf.ctypes.data, slot_stride, ln.ctypes.data, n, out.ctypes.data,
-                         AIPSTACK_CHKSUM_FINAL if final else 0)
-        return t, out
-
-    def submit_rx_verify_slotted(self, frames, slot_stride: int, lens, *, out=None):
-        ln, n = ChksumEngine._slot_args(frames, slot_stride, lens)
-        ln = ln.copy()  # (as submit_slotted)
-        out = ChksumEngine._host_args(frames, out, n, np.uint8)
-        t = self._submit("aipstack_chksum_engine_group_submit_rx_verify_slotted",
-                         (frames, ln, out), frames.ctypes.data, slot_stride, ln.ctypes.data, n,
-                         out.ctypes.data)
-        return t, out
-
-    def submit_tx_fill_slotted(self, frames, slot_stride: int, lens, *, status=None):
-        if not frames.flags.writeable:
-            raise ValueError("frames must be writable (filled in place)")
-        ln, n = ChksumEngine._slot_args(frames, slot_stride, lens)
-        ln = ln.copy()  # (as submit_slotted)
-        status = ChksumEngine._host_args(frames, status, n, np.uint8)
-        t = self._submit("aipstack_chksum_engine_group_submit_tx_fill_slotted",
-                         (frames, ln, status), frames.ctypes.data, slot_stride, ln.ctypes.data,
-                         n, status.ctypes.data)
-        return t, status
-
-    def strided(self, buf, stride: int, length: int, n: int, *, out=None, final=False):
-        if n and (n - 1) * stride + length > buf.nbytes:
-            raise ValueError("batch exceeds buf")
-        out = ChksumEngine._host_args(buf, out, n)
-        self._call("aipstack_chksum_engine_group_host_strided", "engine group strided",
-                   buf.ctypes.data, stride, length, n, out.ctypes.data,
-                   AIPSTACK_CHKSUM_FINAL if final else 0)
-        return out
-
-    def csr(self, buf, offsets, *, out=None, final=False):
-        o = _host_u64(offsets)
-        n = o.size - 1
-        if n > 0 and int(o[-1]) > buf.nbytes:
-            raise ValueError("offsets exceed buf")
-        out = ChksumEngine._host_args(buf, out, n)
-        self._call("aipstack_chksum_engine_group_host_csr", "engine group csr", buf.ctypes.data,
-                   o.ctypes.data, max(n, 0), out.ctypes.data, AIPSTACK_CHKSUM_FINAL if final else 0)
-        return out
-
-    def rx_verify(self, frames, offsets, *, out=None):
-        o = _host_u64(offsets)
-        n = o.size - 1
-        if n > 0 and int(o[-1]) > frames.nbytes:
-            raise ValueError("offsets exceed frames")
-        out = ChksumEngine._host_args(frames, out, n, np.uint8)
-        self._call("aipstack_chksum_engine_group_host_rx_verify", "engine group rx_verify",
-                   frames.ctypes.data, o.ctypes.data, max(n, 0), out.ctypes.data)
-        return out
-
-    def tx_fill(self, frames, offsets, *, status=None):
-        o, n, status = ChksumEngine._tx_args(frames, offsets, status)
-        self._call("aipstack_chksum_engine_group_host_tx_fill", "engine group tx_fill",
-                   frames.ctypes.data, o.ctypes.data, max(n, 0), status.ctypes.data)
-        return status
-
-    # ring slots: frame i = the lens[i] bytes at buf[i * slot_stride:]
-    def slotted(self, buf, slot_stride: int, lens, *, out=None, final=False):
-        ln, n = ChksumEngine._slot_args(buf, slot_stride, lens)
-        out = ChksumEngine._host_args(buf, out, n)
-        self._call("aipstack_chksum_engine_group_host_slotted", "engine group slotted",
-                   buf.ctypes.data, slot_stride, ln.ctypes.data, n, out.ctypes.data,
-                   AIPSTACK_CHKSUM_FINAL if final else 0)
-        return out
-
-    def rx_verify_slotted(self, frames, slot_stride: int, lens, *, out=None):
-        ln, n = ChksumEngine._slot_args(frames, slot_stride, lens)
-        out = ChksumEngine._host_args(frames, out, n, np.uint8)
-        self._call("aipstack_chksum_engine_group_host_rx_verify_slotted",
-                   "engine group rx_verify_slotted", frames.ctypes.data, slot_stride,
-                   ln.ctypes.data, n, out.ctypes.data)
-        return out
-
-    def tx_fill_slotted(self, frames, slot_stride: int, lens, *, status=None):
-        if not frames.flags.writeable:
-            raise ValueError("frames must be writable (filled in place)")
-        ln, n = ChksumEngine._slot_args(frames, slot_stride, lens)
-        status = ChksumEngine._host_args(frames, status, n, np.uint8)
-        self._call("aipstack_chksum_engine_group_host_tx_fill_slotted",
-                   "engine group tx_fill_slotted", frames.ctypes.data, slot_stride,
-                   ln.ctypes.data, n, status.ctypes.data)
-        return status
+# The host-memory engines (numpy arrays in, numpy arrays out) live in engine.py, which takes
+# ChksumError and the status constants from the top of this module.
+from .engine import ChksumEngine, ChksumEngineGroup, _host_u32, _host_u64  # noqa: E402,F401
 
 
 def chksum_batch_chain(chunk_addr, chunk_len, chunk_index, states=None, *, out=None,
@@ -1465,6 +924,21 @@ def _rx_parse_table(pcbs, frames):
     return (pcbs.data_ptr() if nbytes else 0), nbytes // 16, pcbs
 
 
+def _rx_parse_call(name, frames, where, n, pcbs, verdict, segs, pcb, stream):
+    """What the two parse entry points share: the outputs, the PCB table (uploaded on the
+    launch stream), the call `name` on n frames laid out by `where`, the table kept alive."""
+    verdict, segs, pcb = _rx_parse_outputs(n, frames, verdict, segs, pcb)
+    launch_stream = _launch_stream(stream, frames.device)
+    with _torch().cuda.stream(launch_stream):  # an upload is ordered before the call
+        tp, tn, keep = _rx_parse_table(pcbs, frames)
+    _check(getattr(_lib.load(), name)(
+        frames.data_ptr(), *where, n, tp, tn, verdict.data_ptr(), segs.data_ptr(),
+        pcb.data_ptr(), _stream_handle(launch_stream)), name)
+    if keep is not None and keep is not pcbs:
+        keep.record_stream(launch_stream)
+    return TcpRxParsed(verdict, segs, pcb)
+
+
 def tcp_rx_parse(frames, offsets, pcbs=None, *, verdict=None, segs=None, pcb=None, stream=None):
     """Rx verify plus the TCP parse on the GPU (``aipstack_tcp_rx_parse``): frame i =
     ``frames[offsets[i]:offsets[i+1]]``. Per frame the verdict of :func:`rx_verify` (an accepted
@@ -1478,16 +952,8 @@ def tcp_rx_parse(frames, offsets, pcbs=None, *, verdict=None, segs=None, pcb=Non
     _require_offsets(offsets)
     _same_device(frames, offsets, "frames and offsets")
     n = max(offsets.numel() - 1, 0)
-    verdict, segs, pcb = _rx_parse_outputs(n, frames, verdict, segs, pcb)
-    launch_stream = _launch_stream(stream, frames.device)
-    with _torch().cuda.stream(launch_stream):  # an upload is ordered before the call
-        tp, tn, keep = _rx_parse_table(pcbs, frames)
-    _check(_lib.load().aipstack_tcp_rx_parse(
-        frames.data_ptr(), offsets.data_ptr(), n, tp, tn, verdict.data_ptr(), segs.data_ptr(),
-        pcb.data_ptr(), _stream_handle(launch_stream)), "aipstack_tcp_rx_parse")
-    if keep is not None and keep is not pcbs:
-        keep.record_stream(launch_stream)
-    return TcpRxParsed(verdict, segs, pcb)
+    return _rx_parse_call("aipstack_tcp_rx_parse", frames, (offsets.data_ptr(),), n, pcbs,
+                          verdict, segs, pcb, stream)
 
 
 def tcp_rx_parse_slotted(frames, slot_stride: int, lens, pcbs=None, *, verdict=None, segs=None,
@@ -1496,17 +962,8 @@ def tcp_rx_parse_slotted(frames, slot_stride: int, lens, pcbs=None, *, verdict=N
     ``frames[i*slot_stride:]``, as :func:`rx_verify_slotted`)."""
     _require_device(frames, "frames")
     n = _require_lens(lens, frames.numel() * frames.element_size(), slot_stride, frames)
-    verdict, segs, pcb = _rx_parse_outputs(n, frames, verdict, segs, pcb)
-    launch_stream = _launch_stream(stream, frames.device)
-    with _torch().cuda.stream(launch_stream):
-        tp, tn, keep = _rx_parse_table(pcbs, frames)
-    _check(_lib.load().aipstack_tcp_rx_parse_slotted(
-        frames.data_ptr(), slot_stride, lens.data_ptr(), n, tp, tn, verdict.data_ptr(),
-        segs.data_ptr(), pcb.data_ptr(), _stream_handle(launch_stream)),
-        "aipstack_tcp_rx_parse_slotted")
-    if keep is not None and keep is not pcbs:
-        keep.record_stream(launch_stream)
-    return TcpRxParsed(verdict, segs, pcb)
+    return _rx_parse_call("aipstack_tcp_rx_parse_slotted", frames,
+                          (slot_stride, lens.data_ptr()), n, pcbs, verdict, segs, pcb, stream)
 
 
 class SplitFrames:
@@ -1603,18 +1060,11 @@ def tx_fill_records(frames, offsets, *, out=None, stream=None):
     ``w0`` = IPv4 header checksum | L4 checksum << 16 and ``w1`` = L4 field offset (bits
     0-7) | write the IPv4 field (8) | write the L4 field (9) | status (16-23); the host
     applies them (:func:`apply_tx_records`). Returns the records (int64 device tensor)."""
-    torch = _torch()
     _require_device(frames, "frames")
     _require_offsets(offsets)
     _same_device(frames, offsets, "frames and offsets")
     n = max(offsets.numel() - 1, 0)
-    if out is None:
-        out = torch.empty(n, dtype=torch.int64, device=frames.device)
-    else:
-        _require_device(out, "out")
-        if out.element_size() != 8 or out.numel() < n:
-            raise ValueError("out must be a 64-bit device tensor with >= n elements")
-        _same_device(out, frames, "out and frames")
+    out = _records_out(out, n, frames)
     _check(_lib.load().aipstack_chksum_tx_fill_records(frames.data_ptr(), offsets.data_ptr(), n,
                                                        out.data_ptr(), _stream_handle(stream, frames)),
            "aipstack_chksum_tx_fill_records")

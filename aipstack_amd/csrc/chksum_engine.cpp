@@ -748,6 +748,33 @@ extern "C" int aipstack_chksum_engine_unregister(aipstack_chksum_engine *e, void
     return AIPSTACK_CHKSUM_EINVAL;
 }
 
+namespace aipstack_amd {
+bool csr_ok(const uint64_t *off, uint64_t n) {
+    for (uint64_t i = 0; i < n; ++i)
+        if (off[i + 1] < off[i] || off[i + 1] - off[i] > AIPSTACK_CHKSUM_MAX_LEN) return false;
+    return true;
+}
+bool slots_ok(uint64_t slot_stride, const uint32_t *h_len, uint64_t n) {
+    if (slot_stride == 0) return false;
+    const uint64_t cap = std::min<uint64_t>(slot_stride, AIPSTACK_CHKSUM_MAX_LEN);
+    for (uint64_t i = 0; i < n; ++i)
+        if (h_len[i] > cap) return false;
+    return true;
+}
+}  // namespace aipstack_amd
+
+namespace {
+// The synchronous calls: submit, then wait (also for the pieces a failed submit enqueued). The
+// ticket is taken by reference: it is read here, after the submit among the arguments has run.
+int finish_sync(aipstack_chksum_engine *e, int st, const uint64_t &t) {
+    if (st != AIPSTACK_CHKSUM_OK) {
+        if (t) (void)aipstack_chksum_engine_wait(e, t);
+        return st;
+    }
+    return aipstack_chksum_engine_wait(e, t);
+}
+}  // namespace
+
 extern "C" int aipstack_chksum_engine_submit_strided(aipstack_chksum_engine *e,
                                                      const void *h_base, uint64_t stride,
                                                      uint32_t len, uint64_t n, uint16_t *h_out,
@@ -778,9 +805,7 @@ namespace {
 template <class Kernel>
 int submit_csr_like(aipstack_chksum_engine *e, const void *h_base, const uint64_t *h_offsets,
                     uint64_t n, void *h_out, uint32_t elem, Kernel kernel, uint64_t *ticket) {
-    for (uint64_t i = 0; i < n; ++i)  // contract check: non-decreasing, each <= 65535
-        if (h_offsets[i + 1] < h_offsets[i] || h_offsets[i + 1] - h_offsets[i] > AIPSTACK_CHKSUM_MAX_LEN)
-            return AIPSTACK_CHKSUM_EINVAL;
+    if (!csr_ok(h_offsets, n)) return AIPSTACK_CHKSUM_EINVAL;
     const char *base = static_cast<const char *>(h_base);
     auto chunker = [&](uint64_t i0, uint64_t *i1, Span *sp) {
         // whole packets while they fit the chunk (binary search on the offsets)
@@ -848,12 +873,8 @@ extern "C" int aipstack_chksum_engine_host_tx_fill(aipstack_chksum_engine *e, vo
     if (!e || !h_base || !h_offsets || !h_status) return AIPSTACK_CHKSUM_EINVAL;
     if (n == 0) return AIPSTACK_CHKSUM_OK;
     uint64_t t = 0;
-    const int st = aipstack_chksum_engine_submit_tx_fill(e, h_base, h_offsets, n, h_status, &t);
-    if (st != AIPSTACK_CHKSUM_OK) {
-        if (t) (void)aipstack_chksum_engine_wait(e, t);
-        return st;
-    }
-    return aipstack_chksum_engine_wait(e, t);
+    return finish_sync(e, aipstack_chksum_engine_submit_tx_fill(e, h_base, h_offsets, n, h_status,
+                                                               &t), t);
 }
 
 extern "C" int aipstack_chksum_engine_host_rx_verify(aipstack_chksum_engine *e, const void *h_base,
@@ -862,12 +883,8 @@ extern "C" int aipstack_chksum_engine_host_rx_verify(aipstack_chksum_engine *e, 
     if (!e || !h_base || !h_offsets || !h_verdicts) return AIPSTACK_CHKSUM_EINVAL;
     if (n == 0) return AIPSTACK_CHKSUM_OK;
     uint64_t t = 0;
-    const int st = aipstack_chksum_engine_submit_rx_verify(e, h_base, h_offsets, n, h_verdicts, &t);
-    if (st != AIPSTACK_CHKSUM_OK) {
-        if (t) (void)aipstack_chksum_engine_wait(e, t);
-        return st;
-    }
-    return aipstack_chksum_engine_wait(e, t);
+    return finish_sync(e, aipstack_chksum_engine_submit_rx_verify(e, h_base, h_offsets, n,
+                                                                 h_verdicts, &t), t);
 }
 
 extern "C" int aipstack_chksum_engine_submit_csr(aipstack_chksum_engine *e, const void *h_base,
@@ -893,10 +910,8 @@ template <class Kernel>
 int submit_slotted_like(aipstack_chksum_engine *e, const void *h_base, uint64_t slot_stride,
                         const uint32_t *h_len, uint64_t n, void *h_out, uint32_t elem,
                         Kernel kernel, uint64_t *ticket) {
-    if (slot_stride == 0 || slot_stride > e->chunk_bytes) return AIPSTACK_CHKSUM_EINVAL;
-    const uint64_t cap = std::min<uint64_t>(slot_stride, AIPSTACK_CHKSUM_MAX_LEN);
-    for (uint64_t i = 0; i < n; ++i)
-        if (h_len[i] > cap) return AIPSTACK_CHKSUM_EINVAL;
+    if (slot_stride > e->chunk_bytes || !slots_ok(slot_stride, h_len, n))
+        return AIPSTACK_CHKSUM_EINVAL;
     const uint64_t per = std::min<uint64_t>(e->chunk_bytes / slot_stride, e->chunk_packets);
     const char *base = static_cast<const char *>(h_base);
     auto chunker = [&](uint64_t i0, uint64_t *i1, Span *sp) {
@@ -976,17 +991,6 @@ extern "C" int aipstack_chksum_engine_submit_tx_fill_slotted(
                                },
                                ticket);
 }
-
-namespace {
-// The synchronous calls: submit, then wait (also for the pieces a failed submit enqueued).
-int finish_sync(aipstack_chksum_engine *e, int st, uint64_t t) {
-    if (st != AIPSTACK_CHKSUM_OK) {
-        if (t) (void)aipstack_chksum_engine_wait(e, t);
-        return st;
-    }
-    return aipstack_chksum_engine_wait(e, t);
-}
-}  // namespace
 
 extern "C" int aipstack_chksum_engine_host_slotted(aipstack_chksum_engine *e, const void *h_base,
                                                    uint64_t slot_stride, const uint32_t *h_len,
@@ -1095,12 +1099,8 @@ extern "C" int aipstack_chksum_engine_host_strided(aipstack_chksum_engine *e, co
     if (!e || !h_base || !h_out || len > AIPSTACK_CHKSUM_MAX_LEN) return AIPSTACK_CHKSUM_EINVAL;
     if (n == 0) return AIPSTACK_CHKSUM_OK;
     uint64_t t = 0;
-    const int st = aipstack_chksum_engine_submit_strided(e, h_base, stride, len, n, h_out, flags, &t);
-    if (st != AIPSTACK_CHKSUM_OK) {
-        if (t) (void)aipstack_chksum_engine_wait(e, t);  // pieces already in flight
-        return st;
-    }
-    return aipstack_chksum_engine_wait(e, t);
+    return finish_sync(e, aipstack_chksum_engine_submit_strided(e, h_base, stride, len, n, h_out,
+                                                               flags, &t), t);
 }
 
 extern "C" int aipstack_chksum_engine_host_csr(aipstack_chksum_engine *e, const void *h_base,
@@ -1109,10 +1109,6 @@ extern "C" int aipstack_chksum_engine_host_csr(aipstack_chksum_engine *e, const 
     if (!e || !h_base || !h_offsets || !h_out) return AIPSTACK_CHKSUM_EINVAL;
     if (n == 0) return AIPSTACK_CHKSUM_OK;
     uint64_t t = 0;
-    const int st = aipstack_chksum_engine_submit_csr(e, h_base, h_offsets, n, h_out, flags, &t);
-    if (st != AIPSTACK_CHKSUM_OK) {
-        if (t) (void)aipstack_chksum_engine_wait(e, t);
-        return st;
-    }
-    return aipstack_chksum_engine_wait(e, t);
+    return finish_sync(e, aipstack_chksum_engine_submit_csr(e, h_base, h_offsets, n, h_out, flags,
+                                                           &t), t);
 }

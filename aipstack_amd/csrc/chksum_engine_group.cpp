@@ -237,22 +237,6 @@ void settle(Part &p, int engine_result) {
     p.status = p.submit_status != AIPSTACK_CHKSUM_OK ? p.submit_status : engine_result;
 }
 
-bool csr_ok(const uint64_t *off, uint64_t n) {
-    for (uint64_t i = 0; i < n; ++i)
-        if (off[i + 1] < off[i] || off[i + 1] - off[i] > AIPSTACK_CHKSUM_MAX_LEN) return false;
-    return true;
-}
-
-// Ring slots (frame i = h_len[i] bytes at h_base + i * slot_stride): every length is checked
-// before any device starts.
-bool slots_ok(uint64_t slot_stride, const uint32_t *h_len, uint64_t n) {
-    if (slot_stride == 0) return false;
-    const uint64_t cap = std::min<uint64_t>(slot_stride, AIPSTACK_CHKSUM_MAX_LEN);
-    for (uint64_t i = 0; i < n; ++i)
-        if (h_len[i] > cap) return false;
-    return true;
-}
-
 // The synchronous calls: submit, then wait (also after a failed submit: its other ranges).
 int sync_call(aipstack_chksum_engine_group *g, int st, uint64_t t, int *dev_status) {
     const int w = t ? aipstack_chksum_engine_group_wait(g, t, dev_status) : st;

@@ -100,6 +100,11 @@ namespace aipstack_amd {
 // Host engine internals shared with the engine group (chksum_engine.cpp).
 // The region (page-locked by the group, portable) as input of this engine too; returns
 // whether the engine's kernels read it in place (mapped into this device's address space).
+// The contracts of a host batch, checked by the engine and, before any device starts, by the
+// group. CSR: n + 1 non-decreasing offsets, each packet <= 65535 bytes. Ring slots (frame i =
+// h_len[i] bytes at h_base + i * slot_stride): a stride, every length <= min(stride, 65535).
+bool csr_ok(const uint64_t *off, uint64_t n);
+bool slots_ok(uint64_t slot_stride, const uint32_t *h_len, uint64_t n);
 bool engine_adopt_region(aipstack_chksum_engine *e, const void *p, uint64_t bytes);
 void engine_drop_region(aipstack_chksum_engine *e, const void *p);
 }  // namespace aipstack_amd
