@@ -65,6 +65,15 @@ _FROM_CHKSUM = [
     "TcpSegments",
     "tcp_burst_layout",
     "tcp_tx_segment",
+    "AIPSTACK_TX_DGRAM_INVALID",
+    "AIPSTACK_TX_FRAG_NEEDED",
+    "AIPSTACK_UDP_FIRST_FRAGMENT_HEADER",
+    "AIPSTACK_UDP_MIN_MTU",
+    "AIPSTACK_UDP_NEXT_FRAGMENT_HEADER",
+    "UDP_DGRAM_DTYPE",
+    "UdpFragments",
+    "udp_dgram_layout",
+    "udp_tx_fragment",
     "AIPSTACK_RX_DROP_TCP_OFFSET",
     "AIPSTACK_TCP_NO_PCB",
     "AIPSTACK_TCP_OPT_MSS",

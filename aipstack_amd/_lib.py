@@ -42,6 +42,11 @@ SIGNATURES = {
     "aipstack_tcp_tx_segment_workspace_bytes": (_c_u64, [_c_u64]),
     "aipstack_tcp_tx_segment": (_c_int, [_c_vp, _c_vp, _c_vp, _c_u64, _c_u64, _c_u64, _c_vp, _c_u64,
                                          _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_u64, _c_u32, _c_vp]),
+    "aipstack_udp_dgram_layout": (_c_int, [_c_vp, _c_u64, _c_vp, _c_vp, _c_vp]),
+    "aipstack_udp_tx_fragment_workspace_bytes": (_c_u64, [_c_u64, _c_u64]),
+    "aipstack_udp_tx_fragment": (_c_int, [_c_vp, _c_vp, _c_vp, _c_u64, _c_u64, _c_u64, _c_vp, _c_u64,
+                                          _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_u64,
+                                          _c_u32, _c_vp]),
     "aipstack_tcp_pcb_table_sort": (_c_int, [_c_vp, _c_u64]),
     "aipstack_tcp_rx_parse": (_c_int, [_c_vp, _c_vp, _c_u64, _c_vp, _c_u64, _c_vp, _c_vp, _c_vp, _c_vp]),
     "aipstack_tcp_rx_parse_slotted": (_c_int, [_c_vp, _c_u64, _c_vp, _c_u64, _c_vp, _c_u64, _c_vp, _c_vp,

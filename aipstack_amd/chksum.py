@@ -827,6 +827,178 @@ def tcp_tx_segment(bursts, seg_index, chunk_base, *, hdr_stride: int = 64, heade
     return res
 
 
+AIPSTACK_UDP_FIRST_FRAGMENT_HEADER = 42   # Ethernet 14 + IPv4 20 + UDP 8
+AIPSTACK_UDP_NEXT_FRAGMENT_HEADER = 34    # Ethernet 14 + IPv4 20: fragments after the first
+AIPSTACK_UDP_MIN_MTU = 256
+AIPSTACK_TX_FRAG_NEEDED = 12       # udp_tx_fragment: above the MTU with DF set, nothing emitted
+AIPSTACK_TX_DGRAM_INVALID = 13     # udp_tx_fragment: the datagram breaks the contract
+
+# ``aipstack_udp_dgram`` (chksum.h): one UDP datagram to send, host-made.
+UDP_DGRAM_DTYPE = np.dtype({
+    "names": ["data_addr", "data_len", "mtu", "ip_id", "reserved", "hdr"],
+    "formats": [("<u8", (2,)), ("<u4", (2,)), "<u2", "<u2", "<u4", ("u1", (48,))],
+    "offsets": [0, 16, 24, 26, 28, 32],
+    "itemsize": 80,
+})
+assert UDP_DGRAM_DTYPE.itemsize == 80
+
+
+def udp_dgram_layout(dgrams):
+    """Host side of :func:`udp_tx_fragment` (``aipstack_udp_dgram_layout``, no GPU): the fragment
+    and chunk counts of each datagram of ``dgrams`` (a ``UDP_DGRAM_DTYPE`` array) as running
+    sums and each datagram's status, ``(frag_index, chunk_base, status)``: uint64 arrays of
+    ``len(dgrams) + 1`` entries and a uint8 array (``AIPSTACK_RX_ACCEPT``, or
+    ``AIPSTACK_TX_FRAG_NEEDED`` for a datagram above its MTU with DF set: no fragment, no
+    chunk). Raises :class:`ChksumError` (``AIPSTACK_CHKSUM_EINVAL``) if a datagram breaks the
+    contract."""
+    g = np.ascontiguousarray(dgrams, dtype=UDP_DGRAM_DTYPE).reshape(-1)
+    frag_index = np.zeros(g.size + 1, dtype=np.uint64)
+    chunk_base = np.zeros(g.size + 1, dtype=np.uint64)
+    status = np.zeros(max(g.size, 1), dtype=np.uint8)
+    _check(_lib.load().aipstack_udp_dgram_layout(g.ctypes.data if g.size else None, g.size,
+                                                 frag_index.ctypes.data, chunk_base.ctypes.data,
+                                                 status.ctypes.data),
+           "aipstack_udp_dgram_layout")
+    return frag_index, chunk_base, status[:g.size]
+
+
+class UdpFragments:
+    """What :func:`udp_tx_fragment` leaves (device tensors): ``headers`` (uint8, n slots of
+    ``hdr_stride`` bytes), ``hdr_lens`` (int32, n: 42 for a datagram's first fragment, 34 for
+    the others, 0 where nothing was emitted), the chunk table ``chunk_addr`` (int64) /
+    ``chunk_len`` (int32) / ``chunk_index`` (int64, n + 1 entries), ``status`` (uint8, n) and
+    ``dgram_status`` (uint8, one per datagram). Headers, lengths and the chunk table are the
+    arguments of :func:`tx_fill_header_split`; the chunk table is what
+    :func:`chksum_batch_chain` takes."""
+
+    def __init__(self, headers, hdr_stride, hdr_lens, chunk_addr, chunk_len, chunk_index, status,
+                 dgram_status):
+        self.headers, self.hdr_stride, self.hdr_lens = headers, hdr_stride, hdr_lens
+        self.chunk_addr, self.chunk_len, self.chunk_index = chunk_addr, chunk_len, chunk_index
+        self.status, self.dgram_status = status, dgram_status
+
+    @property
+    def n_frags(self) -> int:
+        return self.chunk_index.numel() - 1
+
+
+def udp_tx_fragment(dgrams, frag_index, chunk_base, *, hdr_stride: int = 64, headers=None,
+                    just_written: bool = False, stream=None, workspace=None, out=None,
+                    n_frags: Optional[int] = None, n_chunks: Optional[int] = None,
+                    device=None) -> UdpFragments:
+    """UDP send with IPv4 fragmentation on the GPU (``aipstack_udp_tx_fragment``): for every
+    datagram of ``dgrams`` (``UDP_DGRAM_DTYPE``), every fragment's complete frame header in slot
+    i of a header ring (one fragment for a datagram that fits its MTU), the chunk table of its
+    data bytes, the IPv4 header checksums and the UDP checksum -- what the reference's
+    ``sendUdpIp4Packet`` / ``sendIp4Dgram`` / ``send_fragmented`` produce.
+
+    ``dgrams``, ``frag_index``, ``chunk_base``: host numpy arrays (the latter two from
+    :func:`udp_dgram_layout`; uploaded here), or device tensors already resident (uint8 /
+    int64 / int64), in which case ``n_frags`` and ``n_chunks`` (the last index entries) must be
+    given. ``headers``: the ring to write (device uint8 tensor of at least n slots of
+    ``hdr_stride`` bytes; else a fresh one). ``out``: a :class:`UdpFragments` whose tensors are
+    reused (``headers`` / ``hdr_stride`` then come from it). ``workspace``: a device tensor of
+    at least ``aipstack_udp_tx_fragment_workspace_bytes(n_dgrams, n)`` bytes, 8-byte aligned.
+    ``just_written``: the AIPSTACK_CHKSUM_JUST_WRITTEN hint for the data read. Status per
+    fragment: ``AIPSTACK_RX_ACCEPT``, or ``AIPSTACK_TX_DGRAM_INVALID`` (slot untouched); per
+    datagram also ``AIPSTACK_TX_FRAG_NEEDED``. With no fragment at all nothing runs and
+    ``dgram_status`` is not written (:func:`udp_dgram_layout` has it)."""
+    torch = _torch()
+    if hasattr(frag_index, "data_ptr"):
+        if n_frags is None or n_chunks is None:
+            raise ValueError("device frag_index/chunk_base need n_frags and n_chunks")
+        for t, name in ((dgrams, "dgrams"), (frag_index, "frag_index"), (chunk_base, "chunk_base")):
+            _require_device(t, name)
+        if frag_index.element_size() != 8 or chunk_base.element_size() != 8:
+            raise ValueError("frag_index/chunk_base must be 64-bit")
+        if frag_index.numel() != chunk_base.numel() or frag_index.numel() < 1:
+            raise ValueError("frag_index and chunk_base must hold n_dgrams + 1 entries each")
+        n_dgrams = frag_index.numel() - 1
+        if dgrams.numel() * dgrams.element_size() < 80 * n_dgrams:
+            raise ValueError("dgrams must hold n_dgrams descriptors of 80 bytes")
+        d_dgrams, d_frag, d_base = dgrams, frag_index, chunk_base
+        dev = dgrams.device
+    else:
+        g = np.ascontiguousarray(dgrams, dtype=UDP_DGRAM_DTYPE).reshape(-1)
+        fi = np.array(frag_index, dtype=np.uint64).reshape(-1)   # (copies: torch wants them writable)
+        cb = np.array(chunk_base, dtype=np.uint64).reshape(-1)
+        if fi.size != g.size + 1 or cb.size != g.size + 1:
+            raise ValueError("frag_index and chunk_base must hold len(dgrams) + 1 entries each")
+        n_dgrams = g.size
+        n_frags = int(fi[-1]) if n_frags is None else n_frags
+        n_chunks = int(cb[-1]) if n_chunks is None else n_chunks
+        if out is not None:
+            dev = out.headers.device
+        elif headers is not None:
+            dev = headers.device
+        else:
+            dev = torch.device("cuda" if device is None else device)
+        raw = np.zeros(max(g.size, 1) * 80, dtype=np.uint8)
+        raw[:g.size * 80] = g.view(np.uint8)
+        with torch.cuda.stream(_launch_stream(stream, dev)):  # uploads ordered before the call
+            d_dgrams = torch.from_numpy(raw).to(dev)
+            d_frag = torch.from_numpy(fi.view(np.int64)).to(dev)
+            d_base = torch.from_numpy(cb.view(np.int64)).to(dev)
+    n, nc = int(n_frags), int(n_chunks)
+    if n < 0 or nc < 0:
+        raise ValueError("n_frags and n_chunks must not be negative")
+    if out is not None:
+        headers, hdr_stride = out.headers, out.hdr_stride
+        for t, name, cnt, size in ((out.hdr_lens, "hdr_lens", n, 4),
+                                   (out.chunk_addr, "chunk_addr", nc, 8),
+                                   (out.chunk_len, "chunk_len", nc, 4),
+                                   (out.chunk_index, "chunk_index", n + 1, 8),
+                                   (out.status, "status", n, 1),
+                                   (out.dgram_status, "dgram_status", n_dgrams, 1)):
+            _require_device(t, f"out.{name}")
+            if t.element_size() != size or t.numel() < cnt:
+                raise ValueError(f"out.{name} is too small or of the wrong element size")
+        if out.chunk_index.numel() != n + 1 or out.status.numel() != n or out.hdr_lens.numel() != n:
+            raise ValueError("out.chunk_index / out.status / out.hdr_lens must hold n + 1 / n / n entries")
+        res = out
+    if hdr_stride < AIPSTACK_UDP_FIRST_FRAGMENT_HEADER:
+        raise ValueError("hdr_stride must be at least 42")
+    if headers is None:
+        headers = torch.zeros(max(n * hdr_stride, 1), dtype=torch.uint8, device=dev)
+    else:
+        _require_device(headers, "headers")
+        if headers.element_size() != 1 or headers.numel() < n * hdr_stride:
+            raise ValueError("headers must be a uint8 tensor of n whole slots of hdr_stride bytes")
+    _same_device(headers, d_dgrams, "headers and dgrams")
+    if out is None:
+        res = UdpFragments(headers, hdr_stride,
+                           torch.zeros(max(n, 1), dtype=torch.int32, device=dev)[:n],
+                           torch.zeros(max(nc, 1), dtype=torch.int64, device=dev)[:nc],
+                           torch.zeros(max(nc, 1), dtype=torch.int32, device=dev)[:nc],
+                           torch.zeros(n + 1, dtype=torch.int64, device=dev),
+                           torch.empty(n, dtype=torch.uint8, device=dev),
+                           torch.zeros(max(n_dgrams, 1), dtype=torch.uint8, device=dev)[:n_dgrams])
+    if n == 0:
+        return res
+    lib = _lib.load()
+    need = int(lib.aipstack_udp_tx_fragment_workspace_bytes(n_dgrams, n))
+    workspace, ws_bytes = _workspace(workspace, need, headers, "headers")
+    launch_stream = _launch_stream(stream, dev)
+    # no chunk at all (empty datagrams) or no datagram: the C-ABI wants non-null arrays
+    ca, cl, ds = res.chunk_addr, res.chunk_len, res.dgram_status
+    if nc == 0 and (ca.data_ptr() == 0 or cl.data_ptr() == 0):
+        ca = torch.zeros(1, dtype=torch.int64, device=dev)
+        cl = torch.zeros(1, dtype=torch.int32, device=dev)
+    if n_dgrams == 0 and ds.data_ptr() == 0:
+        ds = torch.zeros(1, dtype=torch.uint8, device=dev)
+    _check(lib.aipstack_udp_tx_fragment(
+        d_dgrams.data_ptr(), d_frag.data_ptr(), d_base.data_ptr(), n_dgrams, n, nc,
+        headers.data_ptr(), hdr_stride, res.hdr_lens.data_ptr(), ca.data_ptr(), cl.data_ptr(),
+        res.chunk_index.data_ptr(), res.status.data_ptr(), ds.data_ptr(), workspace.data_ptr(),
+        ws_bytes, AIPSTACK_CHKSUM_JUST_WRITTEN if just_written else 0,
+        _stream_handle(launch_stream)), "aipstack_udp_tx_fragment")
+    # the allocator must not reuse the workspace or the uploaded descriptors before the launch
+    # stream has passed the call
+    for t in (workspace, d_dgrams, d_frag, d_base, ca, cl, ds):
+        t.record_stream(launch_stream)
+    return res
+
+
 AIPSTACK_RX_DROP_TCP_OFFSET = 11    # tcp_rx_parse: TCP checksum good, data offset out of range
 AIPSTACK_TCP_NO_PCB = 0xFFFFFFFF
 AIPSTACK_TCP_OPT_MSS = 1            # = TcpOptionFlags::Mss

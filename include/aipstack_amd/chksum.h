@@ -356,6 +356,115 @@ int aipstack_tcp_tx_segment(const aipstack_tcp_burst *d_bursts, const uint64_t *
                             void *d_workspace, uint64_t workspace_bytes,
                             uint32_t flags, void *stream);
 
+/* ---- UDP send with IPv4 fragmentation: headers, chunk table and checksums of datagrams --- */
+
+/* The reference sends a UDP datagram through UdpApi::sendUdpIp4Packet -> IpStack::sendIp4Dgram ->
+ * send_fragmented (udp/IpUdpProto.h:152-184, ip/IpStack.h:373-464, 467-539): one UDP checksum
+ * over the whole datagram, then one IPv4 packet per fragment in which only the total length, the
+ * flags / fragment offset and the header checksum change while a range of the datagram's buffer
+ * is cut into pieces. This is that loop for a batch of datagrams: the host hands over one
+ * descriptor per datagram, the GPU emits every fragment's frame header (one, for a datagram that
+ * fits its MTU), the chunk table of its data, the IPv4 header checksums and the UDP checksum, in
+ * the layout aipstack_chksum_tx_fill_hsplit, aipstack_chksum_batch_chain and a scatter-gather
+ * sender take. Routing, the source-address check (checkSendIp4Allowed), ARP and the decision to
+ * send stay with the host; ICMP sends and IPv4 options are not covered. */
+#define AIPSTACK_UDP_FIRST_FRAGMENT_HEADER 42u /* Ethernet 14 + IPv4 20 (IHL 5) + UDP 8 */
+#define AIPSTACK_UDP_NEXT_FRAGMENT_HEADER  34u /* Ethernet 14 + IPv4 20: fragments after the first */
+#define AIPSTACK_UDP_MIN_MTU 256u              /* the reference's MinMTU (ip/IpStack.h:255) */
+#define AIPSTACK_TX_FRAG_NEEDED   12 /* per datagram: above the MTU with DF set
+                                        (IpErr::FragmentationNeeded, ip/IpStack.h:409-411) */
+#define AIPSTACK_TX_DGRAM_INVALID 13 /* per fragment / datagram: the datagram breaks the contract */
+
+typedef struct aipstack_udp_dgram {       /* 80 bytes, 8-byte aligned, host-made */
+    uint64_t data_addr[2];  /* DEVICE addresses of the UDP payload: at most two pieces, piece 1
+                               follows piece 0; any alignment (as aipstack_tcp_burst) */
+    uint32_t data_len[2];   /* bytes in each piece; D = their sum, 8 + D <= 65535 */
+    uint16_t mtu;           /* IP MTU of the outgoing interface, >= AIPSTACK_UDP_MIN_MTU */
+    uint16_t ip_id;         /* Ident of the datagram: EVERY fragment carries it (m_next_id++ runs
+                               once per datagram, ip/IpStack.h:434) */
+    uint32_t reserved;      /* 0 */
+    uint8_t  hdr[48];       /* template, first 42 bytes: Ethernet 14 + IPv4 20 + UDP 8 as
+                               Ip4CommonSendParams and UdpTxInfo would fill them */
+} aipstack_udp_dgram;
+
+/* Fragments of a datagram, with P = 8 + D (the IP payload), M = mtu - 20 and F = (M / 8) * 8
+ * (Ip4RoundFragLen(20, mtu) - 20, proto/Ip4Proto.h:71-73):
+ *   - 20 + P <= mtu: S = 1; total length 20 + P; flags / offset the template's (DF allowed);
+ *   - else, DF set in the template: S = 0, nothing is emitted, datagram status
+ *     AIPSTACK_TX_FRAG_NEEDED (not an error);
+ *   - else S = ceil((P - M) / F) + 1: fragment k < S - 1 carries the F bytes at IP-payload offset
+ *     k * F with MF set, the last one the rest (up to M bytes: more than F when M is not a
+ *     multiple of 8, ip/IpStack.h:497-501); flags / offset (k < S - 1 ? 0x2000 : 0) | k * F / 8;
+ *     total length 20 + the fragment's payload bytes.
+ * Every fragment: the datagram's Ident; the IPv4 header checksum over its 20 header bytes
+ * (ip/IpStack.h:425-453 and :510-515 give the same value). Fragment 0 carries the UDP header:
+ * length P, checksum over the pseudo-header (addresses, 17, P), the UDP header and the whole
+ * payload, a computed 0 sent as 0xFFFF (udp/IpUdpProto.h:163-179).
+ * Template: copied are the MACs, EtherType, version/IHL/DSCP, the DF bit, TTL, protocol, addresses
+ * and ports; ignored and overwritten are the IPv4 total length, Ident, MF and fragment offset, the
+ * header checksum, the UDP length and the UDP checksum.
+ * Data, in UDP-payload coordinates: fragment 0 owns [0, F - 8) ([0, D) when S = 1), fragment
+ * k >= 1 owns [k * F - 8, ...): one chunk, two for the one fragment that straddles the piece
+ * boundary, none when D = 0. C = the datagram's chunk count.
+ *
+ * Datagram contract: mtu >= 256; 8 + D <= 65535; reserved == 0; template EtherType 0x0800,
+ * version/IHL 0x45, protocol 17, flags / offset word with no bit but DF; frag_index[d+1] -
+ * frag_index[d] == S and chunk_base[d+1] - chunk_base[d] == C. */
+
+/* Host side, no GPU: fragment and chunk counts of each datagram as running sums (n_dgrams + 1
+ * entries each, starting at 0) and, if h_status is not NULL, each datagram's status
+ * (AIPSTACK_RX_ACCEPT, or AIPSTACK_TX_FRAG_NEEDED with S = C = 0); _EINVAL if a datagram breaks
+ * the contract above (or for a null pointer, n_dgrams > 2^40). */
+int aipstack_udp_dgram_layout(const aipstack_udp_dgram *h_dgrams, uint64_t n_dgrams,
+                              uint64_t *h_frag_index, uint64_t *h_chunk_base, uint8_t *h_status);
+
+/* <= 16 * (n_dgrams + n_frags) + 256 */
+uint64_t aipstack_udp_tx_fragment_workspace_bytes(uint64_t n_dgrams, uint64_t n_frags);
+
+/* The batch. d_dgrams, d_frag_index, d_chunk_base: the descriptors and the two running sums of
+ * aipstack_udp_dgram_layout, in DEVICE memory (non-decreasing, from 0 to n_frags / n_chunks).
+ * Fragment i is the k-th fragment of the datagram d that holds it (frag_index[d] <= i <
+ * frag_index[d+1], k = i - frag_index[d]). The call leaves:
+ *   - its header at d_hdr + i*hdr_stride: 42 bytes (Ethernet, IPv4, UDP) for k = 0, 34 bytes
+ *     (Ethernet, IPv4) for k >= 1, d_hdr_len[i] saying which; the slot's bytes from the header's
+ *     end up to min(hdr_stride, 64) written as 0 (a 64-byte ring on a 64-byte boundary is stored
+ *     in whole lines), bytes past 64 untouched; slots are written once, whole, and never read;
+ *   - a compact chunk table in the form and contract of aipstack_chksum_batch_chain (no empty
+ *     chunks; d_chunk_index[n_frags] = n_chunks; n_chunks entries of d_chunk_addr / d_chunk_len,
+ *     n_frags + 1 of d_chunk_index). Within a datagram, fragment k's first chunk is
+ *     chunk_base[d] + k, plus 1 if k lies after the straddling fragment;
+ *   - d_status[i] = AIPSTACK_RX_ACCEPT, and per datagram d_dgram_status[d] = AIPSTACK_RX_ACCEPT
+ *     or AIPSTACK_TX_FRAG_NEEDED.
+ * The bytes are what the reference's three functions produce, and for a datagram of one fragment
+ * what aipstack_chksum_tx_fill_hsplit leaves when run on the same header with both fields zeroed.
+ * A datagram that breaks the contract: d_dgram_status[d] = AIPSTACK_TX_DGRAM_INVALID, every
+ * fragment the caller's index gives it gets that status and d_hdr_len 0, its slots stay
+ * untouched, and its chunk entries are written with length 0 at address 0 (harmless to the
+ * chained batch); so is a fragment or a chunk entry that the index gives to no datagram.
+ * Whatever the descriptors and the two indices hold, only the n_frags slots, d_hdr_len, the
+ * n_chunks entries (every one of them, by the lane of its own number), the index, the two status
+ * arrays and the workspace are written, and the payload is read only through table entries
+ * written by this call.
+ *
+ * Three stream-ordered passes through the caller's workspace (8-byte aligned, at least
+ * aipstack_udp_tx_fragment_workspace_bytes(n_dgrams, n_frags) bytes, free again once the stream
+ * passes the call): a plan pass (owner search, validation, chunk table, per-fragment IPv4
+ * checksum, per-datagram UDP seed and chain bounds), the chained batch with ONE CHAIN PER
+ * DATAGRAM (a datagram's fragments partition its payload in order, so the chunks
+ * [chunk_base[d], chunk_base[d+1]) of the table just written are its chain), an emit pass that
+ * builds and stores the slots. Never allocates or synchronises; can be captured into a graph and
+ * repeated (outputs depend on inputs only). flags: AIPSTACK_CHKSUM_JUST_WRITTEN (the payload
+ * read); other bits are ignored. _EINVAL before any work for a null pointer, hdr_stride < 42,
+ * n_dgrams / n_frags / n_chunks above 2^40, a short or misaligned workspace; n_frags == 0 is a
+ * no-op. */
+int aipstack_udp_tx_fragment(const aipstack_udp_dgram *d_dgrams, const uint64_t *d_frag_index,
+                             const uint64_t *d_chunk_base, uint64_t n_dgrams, uint64_t n_frags,
+                             uint64_t n_chunks, void *d_hdr, uint64_t hdr_stride,
+                             uint32_t *d_hdr_len, uint64_t *d_chunk_addr, uint32_t *d_chunk_len,
+                             uint64_t *d_chunk_index, uint8_t *d_status, uint8_t *d_dgram_status,
+                             void *d_workspace, uint64_t workspace_bytes, uint32_t flags,
+                             void *stream);
+
 /* ---- TCP Rx parse: segment metadata, options and PCB lookup of a batch of frames -------- */
 
 /* What the reference does with a TCP datagram once its checksum is good, up to the call of
@@ -702,7 +811,8 @@ int aipstack_chksum_device_check(int device);
  * default), "lds_pad" (bytes of dynamic LDS per workgroup of the batch, chain and frame
  * kernels, which caps the workgroups per CU; -1 none, 0 the launch's own), "aux_blocks" (most
  * workgroups of a one-element-per-lane pass -- the header-split fill's two, the burst
- * segmentation's plan and emit, the Rx parse, the split Tx fills' scatter: 1 or more; -1 = the
+ * segmentation's and the UDP fragmentation's plan and emit, the Rx parse, the split Tx fills'
+ * scatter: 1 or more; -1 = the
  * default, 64 per CU; tests set 1 or 3 so that a small batch loops). Sweep builds only
  * (tools/build_variant.sh NAME -DAIPSTACK_ALL_VARIANTS; the product build rejects values other
  * than the default): "unroll" (segments per lane issued up front, 1..4), "packets" (packets a

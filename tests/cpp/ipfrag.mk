@@ -1,0 +1,18 @@
+# UDP send with IPv4 fragmentation: the host code (aipstack_amd/csrc/ipfrag_host.cpp, plain C++
+# without a HIP call) and its stand-alone test under AddressSanitizer + UBSan.
+#   make -C tests/cpp -f ipfrag.mk        build/asan/ipfrag_layout_test
+ROCM    ?= /opt/rocm
+ROOT    := ../..
+CSRC    := $(ROOT)/aipstack_amd/csrc
+CLANGXX := $(ROCM)/lib/llvm/bin/clang++
+SAN     := -fsanitize=address,undefined -fno-sanitize-recover=undefined
+
+all: build/asan/ipfrag_layout_test
+
+build/asan/ipfrag_layout_test: ipfrag_layout_test.cpp $(CSRC)/ipfrag_host.cpp $(CSRC)/ipfrag_common.h \
+                               $(ROOT)/include/aipstack_amd/chksum.h
+	@mkdir -p build/asan
+	$(CLANGXX) -g -O1 -fno-omit-frame-pointer -std=c++17 -Wall -Wextra $(SAN) -I$(ROOT)/include -I$(CSRC) \
+	    -o $@ ipfrag_layout_test.cpp $(CSRC)/ipfrag_host.cpp
+
+.PHONY: all
