@@ -85,6 +85,16 @@ _FROM_CHKSUM = [
     "tcp_pcb_table_sort",
     "tcp_rx_parse",
     "tcp_rx_parse_slotted",
+    "AIPSTACK_IP4_MAX_REASS_SIZE",
+    "AIPSTACK_REASS_NONE",
+    "AIPSTACK_RX_DROP_FRAG",
+    "AIPSTACK_RX_FRAG_MEMBER",
+    "AIPSTACK_RX_REASS_TRUNCATED",
+    "IP4_DGRAM_DTYPE",
+    "Ip4Reassembled",
+    "ip4_reass_workspace_bytes",
+    "ip4_rx_reassemble",
+    "ip4_rx_reassemble_slotted",
 ]
 globals().update((name, getattr(chksum, name)) for name in _FROM_CHKSUM)
 

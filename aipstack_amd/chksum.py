@@ -1138,6 +1138,123 @@ def tcp_rx_parse_slotted(frames, slot_stride: int, lens, pcbs=None, *, verdict=N
                           (slot_stride, lens.data_ptr()), n, pcbs, verdict, segs, pcb, stream)
 
 
+AIPSTACK_RX_FRAG_MEMBER = 14       # ip4_rx_reassemble: fragment of a datagram reassembled in this batch
+AIPSTACK_RX_DROP_FRAG = 15         # ip4_rx_reassemble: fragment reassembleIp4 ignores or rejects by itself
+AIPSTACK_RX_REASS_TRUNCATED = 16   # per datagram: UDP length below the reassembled length
+AIPSTACK_REASS_NONE = 0xFFFFFFFF
+AIPSTACK_IP4_MAX_REASS_SIZE = 65531
+
+# ``aipstack_ip4_dgram`` (chksum.h): one reassembled datagram, at its head frame's index.
+IP4_DGRAM_DTYPE = np.dtype({
+    "names": ["n_frags", "last_frame", "data_len", "proto", "verdict", "reserved"],
+    "formats": ["<u4", "<u4", "<u2", "u1", "u1", "<u4"],
+    "offsets": [0, 4, 8, 10, 11, 12],
+    "itemsize": 16,
+})
+assert IP4_DGRAM_DTYPE.itemsize == 16
+
+
+def ip4_reass_workspace_bytes(n: int) -> int:
+    """``aipstack_ip4_reass_workspace_bytes``: the workspace :func:`ip4_rx_reassemble` needs for
+    n frames."""
+    return int(_lib.load().aipstack_ip4_reass_workspace_bytes(max(n, 0)))
+
+
+class Ip4Reassembled:
+    """What :func:`ip4_rx_reassemble` leaves (device tensors, n frames): ``verdict`` (uint8),
+    ``chunk_addr`` (int64: device addresses), ``chunk_len``, ``next``, ``head`` (int32; the bit
+    pattern of ``AIPSTACK_REASS_NONE`` = -1 for no link) and ``dgram`` (uint8, n * 16 bytes: n
+    ``aipstack_ip4_dgram`` records, zero except at head frames)."""
+
+    def __init__(self, verdict, chunk_addr, chunk_len, next, head, dgram):  # noqa: A002
+        self.verdict, self.chunk_addr, self.chunk_len = verdict, chunk_addr, chunk_len
+        self.next, self.head, self.dgram = next, head, dgram
+
+    @property
+    def n(self) -> int:
+        return self.verdict.numel()
+
+    def dgram_numpy(self) -> np.ndarray:
+        """The datagram records on the host as an ``IP4_DGRAM_DTYPE`` array (synchronises)."""
+        return self.dgram[:self.n * 16].cpu().numpy().view(IP4_DGRAM_DTYPE)
+
+    def next_numpy(self) -> np.ndarray:
+        return self.next[:self.n].cpu().numpy().view(np.uint32)
+
+    def head_numpy(self) -> np.ndarray:
+        return self.head[:self.n].cpu().numpy().view(np.uint32)
+
+
+def _reass_out(t, n, itemsize, dtype, frames, name):
+    torch = _torch()
+    if t is None:
+        return torch.empty(n, dtype=dtype, device=frames.device)
+    _require_device(t, name)
+    if t.element_size() != itemsize or t.numel() < n:
+        raise ValueError(f"{name} must be a device tensor of >= n {itemsize}-byte elements")
+    _same_device(t, frames, f"{name} and frames")
+    return t
+
+
+def _reass_call(name, frames, where, n, max_reass_size, verdict, chunk_addr, chunk_len, next,  # noqa: A002
+                head, dgram, workspace, stream):
+    """What the two reassembly entry points share: the outputs, the workspace, the call `name`
+    on n frames laid out by `where`."""
+    torch = _torch()
+    lib = _lib.load()
+    verdict = _u8_out(verdict, n, frames)
+    chunk_addr = _reass_out(chunk_addr, n, 8, torch.int64, frames, "chunk_addr")
+    chunk_len = _reass_out(chunk_len, n, 4, torch.int32, frames, "chunk_len")
+    next = _reass_out(next, n, 4, torch.int32, frames, "next")  # noqa: A001
+    head = _reass_out(head, n, 4, torch.int32, frames, "head")
+    dgram = _reass_out(dgram, n * 16, 1, torch.uint8, frames, "dgram")
+    need = int(lib.aipstack_ip4_reass_workspace_bytes(n))
+    workspace, ws_bytes = _workspace(workspace, need, frames, "frames")
+    launch_stream = _launch_stream(stream, frames.device)
+    _check(getattr(lib, name)(
+        frames.data_ptr(), *where, n, max_reass_size, verdict.data_ptr(), chunk_addr.data_ptr(),
+        chunk_len.data_ptr(), next.data_ptr(), head.data_ptr(), dgram.data_ptr(),
+        workspace.data_ptr(), ws_bytes, _stream_handle(launch_stream)), name)
+    workspace.record_stream(launch_stream)
+    return Ip4Reassembled(verdict, chunk_addr, chunk_len, next, head, dgram)
+
+
+def ip4_rx_reassemble(frames, offsets, *, max_reass_size: int = AIPSTACK_IP4_MAX_REASS_SIZE,
+                      verdict=None, chunk_addr=None, chunk_len=None, next=None, head=None,  # noqa: A002
+                      dgram=None, workspace=None, stream=None):
+    """Rx verify plus IPv4 reassembly on the GPU (``aipstack_ip4_rx_reassemble``): frame i =
+    ``frames[offsets[i]:offsets[i+1]]``. The fragments of the batch are grouped by (source,
+    destination, ident, protocol); a group that is one complete datagram (``max_reass_size`` = the
+    reference's ``MaxReassSize``) gets verdict ``AIPSTACK_RX_FRAG_MEMBER`` on every member, its
+    members linked in offset order (``head``, ``next``) and, at its head frame, an
+    ``aipstack_ip4_dgram`` record with the verdict of the TCP / UDP / ICMP checksum over the
+    linked payload; every other group is left whole for the host's reassembly (verdict 3), but
+    for empty and oversize fragments (``AIPSTACK_RX_DROP_FRAG``). ``chunk_addr`` / ``chunk_len``
+    give every fragment's payload where it lies: nothing is copied. ``workspace``: a device tensor
+    of at least :func:`ip4_reass_workspace_bytes` bytes, else one is taken from torch's allocator.
+    Returns an :class:`Ip4Reassembled`."""
+    _require_device(frames, "frames")
+    _require_offsets(offsets)
+    _same_device(frames, offsets, "frames and offsets")
+    n = max(offsets.numel() - 1, 0)
+    return _reass_call("aipstack_ip4_rx_reassemble", frames, (offsets.data_ptr(),), n,
+                       max_reass_size, verdict, chunk_addr, chunk_len, next, head, dgram, workspace,
+                       stream)
+
+
+def ip4_rx_reassemble_slotted(frames, slot_stride: int, lens, *,
+                              max_reass_size: int = AIPSTACK_IP4_MAX_REASS_SIZE, verdict=None,
+                              chunk_addr=None, chunk_len=None, next=None, head=None, dgram=None,  # noqa: A002
+                              workspace=None, stream=None):
+    """:func:`ip4_rx_reassemble` on a ring of frame slots (frame i = the lens[i] bytes at
+    ``frames[i*slot_stride:]``, as :func:`rx_verify_slotted`)."""
+    _require_device(frames, "frames")
+    n = _require_lens(lens, frames.numel() * frames.element_size(), slot_stride, frames)
+    return _reass_call("aipstack_ip4_rx_reassemble_slotted", frames, (slot_stride, lens.data_ptr()),
+                       n, max_reass_size, verdict, chunk_addr, chunk_len, next, head, dgram,
+                       workspace, stream)
+
+
 class SplitFrames:
     """What :func:`split_frames` returns (host arrays): ``headers`` (n slots of ``hdr_stride``
     bytes), ``hdr_lens`` (uint32), ``payload`` (uint8, every chunk's bytes) and ``chunks``
@@ -1274,7 +1391,8 @@ def apply_tx_records(frames: np.ndarray, offsets: np.ndarray, records: np.ndarra
 
 RX_VERDICTS = {0: "NOT_IP4", 1: "DROP_IP_MALFORMED", 2: "DROP_IP_CHKSUM", 3: "FRAGMENT",
                4: "DROP_L4_MALFORMED", 5: "DROP_L4_CHKSUM", 6: "ACCEPT",
-               7: "ACCEPT_NO_CHKSUM", 8: "ACCEPT_OTHER", 11: "DROP_TCP_OFFSET"}
+               7: "ACCEPT_NO_CHKSUM", 8: "ACCEPT_OTHER", 11: "DROP_TCP_OFFSET",
+               14: "FRAG_MEMBER", 15: "DROP_FRAG", 16: "REASS_TRUNCATED"}
 
 
 def flatten_chains(refs, host_base: np.ndarray, device_base: int):

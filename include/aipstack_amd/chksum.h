@@ -538,6 +538,94 @@ int aipstack_tcp_rx_parse_slotted(const void *d_base, uint64_t slot_stride, cons
                                   uint8_t *d_verdict, aipstack_tcp_rx_seg *d_segs, uint32_t *d_pcb,
                                   void *stream);
 
+/* ---- IPv4 reassembly on receive: fragments linked into datagrams, checksum verified ------ */
+
+/* What the reference does with a fragment between the IPv4 header checks and recvIp4Dgram
+ * (ip/IpStack.h:1020-1043, IpReassembly::reassembleIp4, ip/IpReassembly.h:181-386) -- for the
+ * datagrams whose fragments all lie in one batch of frames, without the copy into a reassembly
+ * buffer (:343-346): the fragments are grouped by the key of find_reass_entry (:409-412: source,
+ * destination, ident, protocol), a group that is one complete datagram is linked in offset order,
+ * and the TCP / UDP / ICMP checksum is taken over the linked payload as recvIp4Dgram's handlers
+ * would take it over the reassembled one (tcp/IpTcpProto_input.h:92-100, udp/IpUdpProto.h:484-489
+ * and :631-652, ip/IpStack.h:1093-1130). The host's Rx loop becomes "for each head: build the
+ * IpBufNode list from d_next, call recvIp4Dgram; feed the verdict-3 fragments to IpReassembly".
+ * Stateless per batch. The local-address test of ip/IpStack.h:1027, expiry, MaxReassEntrys /
+ * MaxReassHoles and anything that spans two batches stay with the host. */
+#define AIPSTACK_RX_FRAG_MEMBER      14  /* per frame: fragment of a datagram reassembled in this batch */
+#define AIPSTACK_RX_DROP_FRAG        15  /* per frame: fragment reassembleIp4 ignores or rejects by itself */
+#define AIPSTACK_RX_REASS_TRUNCATED  16  /* per datagram: complete, UDP length < reassembled length: host verifies */
+#define AIPSTACK_REASS_NONE 0xFFFFFFFFu
+
+typedef struct aipstack_ip4_dgram {   /* 16 bytes, host byte order; all zero except at a head frame */
+    uint32_t n_frags;                 /* >= 2 */
+    uint32_t last_frame;              /* frame index of the fragment without MF */
+    uint16_t data_len;                /* reassembled IP payload length */
+    uint8_t  proto;
+    uint8_t  verdict;                 /* AIPSTACK_RX_ACCEPT / _ACCEPT_NO_CHKSUM / _ACCEPT_OTHER /
+                                         _DROP_L4_MALFORMED / _DROP_L4_CHKSUM / _REASS_TRUNCATED */
+    uint32_t reserved;                /* 0 */
+} aipstack_ip4_dgram;
+
+/* The batch (frames as aipstack_chksum_rx_verify / _rx_verify_slotted take them, under the same
+ * offsets, span and slot contracts). max_reass_size = the reference's MaxReassSize, 1 .. 65531
+ * (ip/IpReassembly.h:96).
+ * A FRAGMENT is a frame Rx verify gives AIPSTACK_RX_FRAGMENT: its IP payload is the total length
+ * - 4*IHL bytes at frame byte 14 + 4*IHL (options allowed), its offset 8 * (flags_offset &
+ * 0x1FFF), its MF bit flags_offset & 0x2000 (ip/IpStack.h:1021-1034). A fragment with an empty
+ * payload belongs to no group (reassembleIp4 returns before touching any state, :189-191):
+ * verdict AIPSTACK_RX_DROP_FRAG. The other fragments with one key form a GROUP. A group is
+ * COMPLETE iff, ordered by offset, its first member has offset 0, each member's offset is the
+ * previous one's offset plus its length, MF is set on every member but the last and clear on the
+ * last, and no member breaks offset <= max_reass_size && length <= max_reass_size - offset
+ * (:219-223). (So: at least two members, no duplicate, no overlap, every length but the last a
+ * multiple of 8.) Arrival order is irrelevant; groups may interleave with each other and with
+ * other traffic. A group is reassembled entirely or left entirely alone:
+ *   - complete: every member gets verdict AIPSTACK_RX_FRAG_MEMBER, d_head[i] = the frame index of
+ *     the offset-0 member, d_next[i] = the frame index of the member with the next offset
+ *     (AIPSTACK_REASS_NONE on the last), and d_dgram[head] is filled;
+ *   - incomplete (a missing piece, a duplicate, an overlap, an extra fragment, two datagrams under
+ *     one key, an oversize member): members that break the size bound get AIPSTACK_RX_DROP_FRAG,
+ *     every other member keeps AIPSTACK_RX_FRAGMENT with AIPSTACK_REASS_NONE links; the host hands
+ *     those to its own IpReassembly in batch order.
+ * Every frame that is no member of a complete group has d_head = d_next = AIPSTACK_REASS_NONE and
+ * every frame that is no head a d_dgram of 16 zero bytes. d_chunk_addr[i] / d_chunk_len[i]: the
+ * payload's device address and length of every fragment with verdict 3 or 14, 0 / 0 for every
+ * other frame (and for a verdict-3 frame whose lengths do not bear the verdict out, which only a
+ * verdict byte changed under the call can give: it stays 3, in no group, nothing of it read); with d_next this is the datagram's IpBufNode list.
+ * Datagram verdict, over data_len = the last member's offset + length: TCP: below 20 bytes
+ * _DROP_L4_MALFORMED, else the checksum with the pseudo-header; UDP: UDP length below 8 or above
+ * data_len _DROP_L4_MALFORMED, else checksum field 0 _ACCEPT_NO_CHKSUM (the host applies the UDP
+ * length, as for a whole frame), else UDP length below data_len AIPSTACK_RX_REASS_TRUNCATED (the
+ * reference truncates the chain there, udp/IpUdpProto.h:492; left to the host), else the checksum;
+ * ICMP: the checksum; any other protocol _ACCEPT_OTHER.
+ *
+ * Stream-ordered passes through the caller's workspace (8-byte aligned, at least
+ * aipstack_ip4_reass_workspace_bytes(n) bytes -- two open-addressing tables of a power of two of
+ * at least 4 entries per frame, cleared by the call, plus 30 bytes per frame -- free again once
+ * the stream passes the call): Rx verify, unchanged; a classify pass (it clears the tables; one
+ * frame per lane: of a fragment at most the 34 first header bytes, never past the frame's own
+ * length whatever the verdict byte says); an insert pass (atomicCAS / atomicOr / atomicAdd on the tables); the chained
+ * batch, unchanged, with one one-chunk chain per frame; a link pass (each member's successor); a
+ * finish pass (one offset-0 member per lane walks its links, at most min(members of its key, 8192)
+ * steps). No lock, no lane waits for another, every probe is bounded by the table size. Never
+ * allocates or synchronises; can be captured into a graph and repeated (outputs depend on inputs
+ * only, never on which lane won a race). _EINVAL before any work for a null pointer, n > 2^32 - 2,
+ * max_reass_size outside 1 .. 65531, d_chunk_addr or the workspace not 8-byte aligned,
+ * d_chunk_len / d_next / d_head / d_dgram not 4-byte aligned, a short workspace, a slot stride
+ * outside (0, AIPSTACK_CHKSUM_MAX_SLOT_STRIDE]; n == 0 is then a no-op. */
+uint64_t aipstack_ip4_reass_workspace_bytes(uint64_t n);
+int aipstack_ip4_rx_reassemble(const void *d_base, const uint64_t *d_offsets, uint64_t n,
+                               uint32_t max_reass_size, uint8_t *d_verdict, uint64_t *d_chunk_addr,
+                               uint32_t *d_chunk_len, uint32_t *d_next, uint32_t *d_head,
+                               aipstack_ip4_dgram *d_dgram, void *d_workspace,
+                               uint64_t workspace_bytes, void *stream);
+int aipstack_ip4_rx_reassemble_slotted(const void *d_base, uint64_t slot_stride,
+                                       const uint32_t *d_len, uint64_t n, uint32_t max_reass_size,
+                                       uint8_t *d_verdict, uint64_t *d_chunk_addr,
+                                       uint32_t *d_chunk_len, uint32_t *d_next, uint32_t *d_head,
+                                       aipstack_ip4_dgram *d_dgram, void *d_workspace,
+                                       uint64_t workspace_bytes, void *stream);
+
 /* ---- 3. host-memory streaming engine ----------------------------------------------- */
 
 /* The reference's packet path starts and ends in host memory (TAP read()/write(),
