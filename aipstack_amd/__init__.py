@@ -95,6 +95,16 @@ _FROM_CHKSUM = [
     "ip4_reass_workspace_bytes",
     "ip4_rx_reassemble",
     "ip4_rx_reassemble_slotted",
+    "AIPSTACK_CHKSUM_MAX_SLOT_STRIDE",
+    "AIPSTACK_TX_LIN_INVALID",
+    "AIPSTACK_TX_LIN_SKIPPED",
+    "AIPSTACK_TX_LIN_TOO_LARGE",
+    "AIPSTACK_TX_LIN_TOO_SHORT",
+    "AIPSTACK_TX_LIN_WRITTEN",
+    "AIPSTACK_TX_LIN_WRONG_ROOM",
+    "LinearFrames",
+    "tx_linearise",
+    "tx_linearise_slotted",
 ]
 globals().update((name, getattr(chksum, name)) for name in _FROM_CHKSUM)
 

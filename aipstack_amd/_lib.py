@@ -38,6 +38,10 @@ SIGNATURES = {
     "aipstack_chksum_tx_fill_hsplit_workspace_bytes": (_c_u64, [_c_u64]),
     "aipstack_chksum_tx_fill_hsplit": (_c_int, [_c_vp, _c_u64, _c_vp, _c_vp, _c_vp, _c_vp, _c_u64,
                                                 _c_vp, _c_vp, _c_u64, _c_u32, _c_vp]),
+    "aipstack_tx_linearise_slotted": (_c_int, [_c_vp, _c_u64, _c_vp, _c_vp, _c_vp, _c_vp, _c_u64, _c_vp,
+                                               _c_vp, _c_u64, _c_u32, _c_vp, _c_vp, _c_u32, _c_vp]),
+    "aipstack_tx_linearise": (_c_int, [_c_vp, _c_u64, _c_vp, _c_vp, _c_vp, _c_vp, _c_u64, _c_vp, _c_vp,
+                                       _c_vp, _c_u32, _c_vp, _c_vp, _c_u32, _c_vp]),
     "aipstack_tcp_burst_layout": (_c_int, [_c_vp, _c_u64, _c_vp, _c_vp]),
     "aipstack_tcp_tx_segment_workspace_bytes": (_c_u64, [_c_u64]),
     "aipstack_tcp_tx_segment": (_c_int, [_c_vp, _c_vp, _c_vp, _c_u64, _c_u64, _c_u64, _c_vp, _c_u64,

@@ -1255,6 +1255,143 @@ def ip4_rx_reassemble_slotted(frames, slot_stride: int, lens, *,
                        workspace, stream)
 
 
+AIPSTACK_TX_LIN_WRITTEN = 17     # tx_linearise: the frame's L bytes are in place
+AIPSTACK_TX_LIN_SKIPPED = 18     # the producer emitted nothing for this segment
+AIPSTACK_TX_LIN_INVALID = 19     # header length, a chunk length or the index breaks the contract
+AIPSTACK_TX_LIN_TOO_SHORT = 20   # L < 14 (sendFrame's HardwareError)
+AIPSTACK_TX_LIN_TOO_LARGE = 21   # L > frame_max (sendFrame's PacketTooLarge)
+AIPSTACK_TX_LIN_WRONG_ROOM = 22  # offsets form: L is not offsets[i+1] - offsets[i]
+AIPSTACK_CHKSUM_MAX_SLOT_STRIDE = 65536
+
+
+class LinearFrames:
+    """What :func:`tx_linearise` / :func:`tx_linearise_slotted` leave: ``frames`` (the caller's
+    uint8 ring, frame i at ``offsets[i]`` or at ``i * slot_stride``; the one that does not apply
+    is None), ``lens`` (int32, n: the frame's length where it was written, else 0) and
+    ``status`` (uint8, n: AIPSTACK_TX_LIN_*). ``frames``, ``slot_stride`` and ``lens`` are the
+    arguments of the ring-slot calls (:func:`rx_verify_slotted`, :func:`tcp_rx_parse_slotted`,
+    :func:`ip4_rx_reassemble_slotted`, :func:`tx_fill_slotted`)."""
+
+    def __init__(self, frames, slot_stride, offsets, lens, status):
+        self.frames, self.slot_stride, self.offsets = frames, slot_stride, offsets
+        self.lens, self.status = lens, status
+
+    @property
+    def n(self) -> int:
+        return self.status.numel()
+
+
+def _linearise_call(name, where, segments, headers, hdr_stride, hdr_lens, chunk_addr, chunk_len,
+                    chunk_index, seg_status, frames, frame_max, lens, status, just_written, stream):
+    torch = _torch()
+    if segments is not None:  # a TcpSegments / UdpFragments object: its tensors and statuses
+        headers, hdr_stride, hdr_lens = segments.headers, segments.hdr_stride, segments.hdr_lens
+        chunk_addr, chunk_len, chunk_index = (segments.chunk_addr, segments.chunk_len,
+                                              segments.chunk_index)
+        seg_status = segments.status if seg_status is None else seg_status
+    tables = [(headers, "headers"), (hdr_lens, "hdr_lens"), (chunk_addr, "chunk_addr"),
+              (chunk_len, "chunk_len"), (chunk_index, "chunk_index")]
+    missing = [tname for t, tname in tables if t is None] + (["hdr_stride"] if hdr_stride is None else [])
+    if missing:
+        raise ValueError("pass `segments` (a TcpSegments / UdpFragments object) or every one of "
+                         "headers, hdr_stride, hdr_lens, chunk_addr, chunk_len, chunk_index; "
+                         f"missing: {', '.join(missing)}")
+    if seg_status is not None:
+        tables.append((seg_status, "seg_status"))
+    for t, tname in tables:
+        _require_device(t, tname)
+        _same_device(headers, t, f"headers and {tname}")
+    if not (frames.is_cuda or frames.is_pinned()) or not frames.is_contiguous() \
+            or frames.element_size() != 1:
+        raise ValueError("frames must be a contiguous uint8 tensor in device or pinned host memory")
+    if chunk_addr.element_size() != 8 or chunk_len.element_size() != 4 \
+            or chunk_index.element_size() != 8:
+        raise ValueError("chunk_addr/chunk_index must be 64-bit, chunk_len 32-bit")
+    if hdr_lens.dtype not in (torch.int32, torch.uint32):
+        raise ValueError("hdr_lens must be an int32/uint32 device tensor")
+    n = chunk_index.numel() - 1
+    if n < 0:
+        raise ValueError("chunk_index must hold n+1 entries")
+    if hdr_lens.numel() < n or (seg_status is not None and
+                                (seg_status.numel() < n or seg_status.element_size() != 1)):
+        raise ValueError("hdr_lens and seg_status (uint8) must hold n entries")
+    if hdr_stride <= 0 or n * hdr_stride > headers.numel() * headers.element_size():
+        raise ValueError("headers must hold n whole slots of hdr_stride bytes")
+    if chunk_addr.numel() != chunk_len.numel():
+        raise ValueError("chunk_addr and chunk_len must hold one entry per chunk")
+    kind, arg = where
+    if kind == "slots":
+        if arg <= 0 or n * arg > frames.numel():
+            raise ValueError("frames must hold n whole slots of slot_stride bytes")
+        place = (int(arg),)
+    else:
+        _require_offsets(arg)
+        _same_device(headers, arg, "headers and offsets")
+        if arg.numel() != n + 1:
+            raise ValueError("offsets must hold n+1 entries")
+        place = (arg.data_ptr(),)
+    if lens is None:
+        lens = torch.empty(n, dtype=torch.int32, device=headers.device)
+    else:
+        _require_device(lens, "lens")
+        if lens.dtype not in (torch.int32, torch.uint32) or lens.numel() < n:
+            raise ValueError("lens must be an int32/uint32 device tensor with >= n elements")
+    status = _u8_out(status, n, headers)
+    if n:
+        stand_in = chunk_addr.numel() == 0
+        if stand_in:  # no chunk at all (pure ACKs): the C-ABI wants non-null tables
+            chunk_addr = torch.zeros(1, dtype=torch.int64, device=headers.device)
+            chunk_len = torch.zeros(1, dtype=torch.int32, device=headers.device)
+        launch_stream = _launch_stream(stream, headers.device)
+        _check(getattr(_lib.load(), name)(
+            headers.data_ptr(), hdr_stride, hdr_lens.data_ptr(), chunk_addr.data_ptr(),
+            chunk_len.data_ptr(), chunk_index.data_ptr(), n,
+            seg_status.data_ptr() if seg_status is not None else None, frames.data_ptr(), *place,
+            int(frame_max), lens.data_ptr(), status.data_ptr(),
+            AIPSTACK_CHKSUM_JUST_WRITTEN if just_written else 0, _stream_handle(launch_stream)),
+            name)
+        if stand_in:  # the allocator must not reuse the stand-in table before the launch is done
+            chunk_addr.record_stream(launch_stream)
+            chunk_len.record_stream(launch_stream)
+    return LinearFrames(frames, arg if kind == "slots" else None,
+                        arg if kind != "slots" else None, lens, status)
+
+
+def tx_linearise_slotted(frames, slot_stride: int, segments=None, *, headers=None, hdr_stride=None,
+                         hdr_lens=None, chunk_addr=None, chunk_len=None, chunk_index=None,
+                         seg_status=None, frame_max: int = 1514, lens=None, status=None,
+                         just_written: bool = False, stream=None) -> LinearFrames:
+    """Linearise header-split Tx segments into the slots of a send ring on the GPU
+    (``aipstack_tx_linearise_slotted``): the batched form of the copy in the reference's
+    ``TapDeviceLinux::sendFrame``. Segment i (the first ``hdr_lens[i]`` bytes of header slot i,
+    then its chunks, as :func:`tx_fill_header_split` takes them) becomes the linear frame at
+    ``frames[i * slot_stride:]``; ``frames`` is a uint8 tensor of n slots in device memory or in
+    pinned host memory. Pass either ``segments`` (a :class:`TcpSegments` or
+    :class:`UdpFragments`: its tensors, its ``hdr_lens``, and its ``status`` as ``seg_status``, so
+    that segments of an invalid burst or datagram are skipped) or the tensors by keyword.
+    ``frame_max``: the frame MTU (at most ``min(slot_stride, 65535)``). Returns
+    :class:`LinearFrames`; nothing outside a written frame's bytes is stored (chksum.h has the
+    outcomes and the byte rules). ``just_written``: the AIPSTACK_CHKSUM_JUST_WRITTEN hint for
+    the payload read (results unchanged)."""
+    return _linearise_call("aipstack_tx_linearise_slotted", ("slots", slot_stride), segments,
+                           headers, hdr_stride, hdr_lens, chunk_addr, chunk_len, chunk_index,
+                           seg_status, frames, frame_max, lens, status, just_written, stream)
+
+
+def tx_linearise(frames, offsets, segments=None, *, headers=None, hdr_stride=None, hdr_lens=None,
+                 chunk_addr=None, chunk_len=None, chunk_index=None, seg_status=None,
+                 frame_max: int = 1514, lens=None, status=None, just_written: bool = False,
+                 stream=None) -> LinearFrames:
+    """As :func:`tx_linearise_slotted` with frame i at ``frames[offsets[i]:offsets[i+1]]``
+    (``aipstack_tx_linearise``; ``offsets``: int64 device tensor of n+1 entries): a segment whose
+    length is not exactly its room is AIPSTACK_TX_LIN_WRONG_ROOM and not written. The result is
+    what :func:`rx_verify`, :func:`tx_fill`, :func:`tcp_rx_parse` and :func:`ip4_rx_reassemble`
+    take when every segment was written."""
+    return _linearise_call("aipstack_tx_linearise", ("csr", offsets), segments, headers, hdr_stride,
+                           hdr_lens, chunk_addr, chunk_len, chunk_index, seg_status, frames,
+                           frame_max, lens, status, just_written, stream)
+
+
 class SplitFrames:
     """What :func:`split_frames` returns (host arrays): ``headers`` (n slots of ``hdr_stride``
     bytes), ``hdr_lens`` (uint32), ``payload`` (uint8, every chunk's bytes) and ``chunks``

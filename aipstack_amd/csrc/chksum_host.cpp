@@ -8,6 +8,7 @@
 #include <atomic>
 #include <cstddef>
 #include <cstdint>
+#include <cstdlib>
 #include <cstring>
 
 #include "aipstack_amd/chksum.h"
@@ -85,6 +86,15 @@ extern "C" int aipstack_chksum_device_check(int device) {
     return AIPSTACK_CHKSUM_OK;
 }
 
+// Violation words of kernel units beyond the two above (add_violation_source, chksum_internal.h);
+// zero-initialised, filled by the units' static initialisers.
+static int (*g_violation_source[4])(uint32_t *, bool);
+static int g_violation_sources;
+void aipstack_amd::add_violation_source(int (*take)(uint32_t *mask, bool clear)) {
+    if (g_violation_sources == 4) std::abort();  // a fifth unit: enlarge the array, never drop a word
+    g_violation_source[g_violation_sources++] = take;
+}
+
 extern "C" int aipstack_chksum_contract_violations(int device, uint32_t *mask, int clear) {
     if (!mask) return AIPSTACK_CHKSUM_EINVAL;
     const int dc = aipstack_chksum_device_check(device);
@@ -96,6 +106,8 @@ extern "C" int aipstack_chksum_contract_violations(int device, uint32_t *mask, i
     uint32_t m = 0;
     if (st == AIPSTACK_CHKSUM_OK) st = take_violations_batch(&m, clear != 0);
     if (st == AIPSTACK_CHKSUM_OK) st = take_violations_frames(&m, clear != 0);
+    for (int k = 0; k < g_violation_sources && st == AIPSTACK_CHKSUM_OK; ++k)
+        st = g_violation_source[k](&m, clear != 0);
     (void)hipSetDevice(prev);
     if (st == AIPSTACK_CHKSUM_OK) *mask = m;
     return st;

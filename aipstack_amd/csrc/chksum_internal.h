@@ -68,6 +68,10 @@ int tx_fill_records_slotted_from(const void *d_base, uint64_t slot_stride, const
                                  uint64_t n, uint64_t *d_records, void *stream, bool host_bytes);
 int take_violations_batch(uint32_t *mask, bool clear);
 int take_violations_frames(uint32_t *mask, bool clear);
+// A further kernel translation unit's word: registered by that unit when the library loads (at
+// most 4: a fifth aborts at load, so that no unit's word is ever left unread), so that a build
+// without the unit links; read by aipstack_chksum_contract_violations.
+void add_violation_source(int (*take)(uint32_t *mask, bool clear));
 
 // Frames a wave of the Rx-verify / Tx-fill kernels keeps in flight (tunable "frames":
 // 2, 4 or 8; default 4).

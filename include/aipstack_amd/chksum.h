@@ -219,8 +219,8 @@ int aipstack_chksum_tx_fill_records_slotted(const void *d_base, uint64_t slot_st
 /* ---- header-split Tx fill: a header ring + send-ring chunks -------------------------- */
 
 /* Status of aipstack_chksum_tx_fill_hsplit: the segment's split does not satisfy the layout
- * rule below; nothing of it was written. The caller linearises such a segment and uses
- * aipstack_chksum_tx_fill. */
+ * rule below; nothing of it was written. The caller linearises such a segment
+ * (aipstack_tx_linearise) and uses aipstack_chksum_tx_fill. */
 #define AIPSTACK_TX_SPLIT_LAYOUT 9
 /* Largest d_hdr_len of the header-split fill. */
 #define AIPSTACK_CHKSUM_MAX_SPLIT_HEADER 256u
@@ -260,6 +260,79 @@ int aipstack_chksum_tx_fill_hsplit(void *d_hdr, uint64_t hdr_stride, const uint3
                                    const uint64_t *d_chunk_index, uint64_t n,
                                    uint8_t *d_status, void *d_workspace,
                                    uint64_t workspace_bytes, uint32_t flags, void *stream);
+
+/* ---- linearise: header-split segments into the linear frames of a send ring ------------ */
+
+/* Per-segment outcomes of aipstack_tx_linearise / aipstack_tx_linearise_slotted. A segment
+ * with several faults takes the earliest in this order: skipped, invalid, too short, too
+ * large, wrong room. */
+#define AIPSTACK_TX_LIN_WRITTEN    17 /* the L bytes of the frame are in place */
+#define AIPSTACK_TX_LIN_SKIPPED    18 /* the producer emitted nothing for this segment */
+#define AIPSTACK_TX_LIN_INVALID    19 /* header length, a chunk length or the index breaks the contract */
+#define AIPSTACK_TX_LIN_TOO_SHORT  20 /* L < 14: sendFrame's HardwareError */
+#define AIPSTACK_TX_LIN_TOO_LARGE  21 /* L > frame_max: sendFrame's PacketTooLarge */
+#define AIPSTACK_TX_LIN_WRONG_ROOM 22 /* offsets form: L is not d_offsets[i+1] - d_offsets[i] */
+
+/* The batched form of the copy in the reference's driver: TapDeviceLinux::sendFrame
+ * (tap/linux/TapDeviceLinux.cpp:109-140) rejects a frame shorter than the Ethernet header
+ * (HardwareError) or longer than the frame MTU (PacketTooLarge), copies the IpBufRef chain into
+ * one linear buffer (ipBufTakeBytes) and write()s it. These calls do the checks and the copy
+ * for n segments at once; the write() and its errno handling stay with the host. The result
+ * is what the ring-slot and CSR calls of this header take (Rx verify, Tx fill, TCP Rx parse,
+ * IPv4 reassembly, the host-memory engine), and what a caller linearises a segment of status
+ * AIPSTACK_TX_SPLIT_LAYOUT with.
+ *
+ * Segment i is what aipstack_chksum_tx_fill_hsplit takes, and what aipstack_tcp_tx_segment and
+ * aipstack_udp_tx_fragment make: the first d_hdr_len[i] bytes at d_hdr + i*hdr_stride, then the
+ * chunks [d_chunk_index[i], d_chunk_index[i+1]) of the chunk table in order (any alignment,
+ * each chunk <= 65535 bytes, n+1 index entries, 0 chunks allowed); L = d_hdr_len[i] + its chunk
+ * bytes. Frame i goes to d_frames + i*slot_stride (0 < slot_stride <=
+ * AIPSTACK_CHKSUM_MAX_SLOT_STRIDE; the ring holds n whole slots) or to d_frames + d_offsets[i]
+ * (n+1 offsets; frame i has the room d_offsets[i+1] - d_offsets[i]).
+ *
+ * d_status[i] (AIPSTACK_TX_LIN_*) and d_frame_len[i] (L where the frame was written, else 0)
+ * are stored for all n segments in every call, so outputs depend on inputs only and a call can
+ * be replayed from a graph:
+ *   skipped     d_hdr_len[i] == 0 (as aipstack_udp_tx_fragment leaves for an invalid datagram),
+ *               or d_seg_status (may be NULL) holds AIPSTACK_TX_BURST_INVALID or
+ *               AIPSTACK_TX_DGRAM_INVALID for it. Every other value of d_seg_status is
+ *               linearised, AIPSTACK_TX_SPLIT_LAYOUT included.
+ *   invalid     d_hdr_len[i] > min(hdr_stride, AIPSTACK_CHKSUM_MAX_SPLIT_HEADER); an index that
+ *               decreases; a chunk over 65535 bytes (also sets the sticky _CHUNK_LEN violation,
+ *               as the chained batch does).
+ *   too short   L < 14.
+ *   too large   L > frame_max.
+ *   wrong room  offsets form: L != d_offsets[i+1] - d_offsets[i].
+ * The chunk lengths are summed in table order and the sum stops after the first chunk that
+ * brings it above frame_max, so a garbage index costs a bounded walk; a chunk over 65535 bytes
+ * behind that point is not looked at (the segment is then too large, not invalid).
+ *
+ * Bytes: nothing outside [frame start, frame start + L) of a written frame is ever stored -- not
+ * a slot's slack, not the slot or room of a skipped or rejected segment, not the bytes between
+ * CSR frames. Reads follow the chained batch: only aligned 16-byte segments that hold a byte of
+ * a header's first d_hdr_len[i] bytes or of a chunk, so a chunk may end at its allocation's
+ * last byte. The destination must not overlap the header ring, any chunk, or the tables; frames
+ * must not overlap each other. Frame stores are nontemporal (the next reader is a DMA engine
+ * or the Rx kernels). No allocation, no synchronisation, no workspace; two stream-ordered
+ * launches (a plan pass, a copy pass), capturable into a graph.
+ *
+ * flags: AIPSTACK_CHKSUM_JUST_WRITTEN is honoured: the payload chunks are then read with
+ * nontemporal loads (header slots always with ordinary ones); results are identical either way.
+ * Other bits are ignored. _EINVAL before any work for a null pointer (d_seg_status excepted), a
+ * zero stride, frame_max == 0, frame_max > 65535, frame_max > slot_stride, slot_stride >
+ * AIPSTACK_CHKSUM_MAX_SLOT_STRIDE, n > 2^40. n == 0 is a no-op that returns _OK before the
+ * arguments are looked at (as aipstack_chksum_tx_fill_hsplit), whatever else is passed. */
+int aipstack_tx_linearise_slotted(const void *d_hdr, uint64_t hdr_stride, const uint32_t *d_hdr_len,
+                                  const uint64_t *d_chunk_addr, const uint32_t *d_chunk_len,
+                                  const uint64_t *d_chunk_index, uint64_t n,
+                                  const uint8_t *d_seg_status, void *d_frames,
+                                  uint64_t slot_stride, uint32_t frame_max, uint32_t *d_frame_len,
+                                  uint8_t *d_status, uint32_t flags, void *stream);
+int aipstack_tx_linearise(const void *d_hdr, uint64_t hdr_stride, const uint32_t *d_hdr_len,
+                          const uint64_t *d_chunk_addr, const uint32_t *d_chunk_len,
+                          const uint64_t *d_chunk_index, uint64_t n, const uint8_t *d_seg_status,
+                          void *d_frames, const uint64_t *d_offsets, uint32_t frame_max,
+                          uint32_t *d_frame_len, uint8_t *d_status, uint32_t flags, void *stream);
 
 /* ---- TCP burst segmentation: headers, chunk table and checksums of a data burst -------- */
 
