@@ -22,6 +22,7 @@ device-memory / stream plumbing here; there is no CPU fallback for the batch cal
 """
 from __future__ import annotations
 
+import collections
 import ctypes
 from typing import Callable, Optional
 
@@ -445,6 +446,40 @@ def chksum_batch_seeded_csr(buf, offsets, states, *, out=None, stream=None):
 from .engine import ChksumEngine, ChksumEngineGroup, _host_u32, _host_u64  # noqa: E402,F401
 
 
+def _chunk_table_count(chunk_addr, chunk_len, chunk_index, fields=None) -> int:
+    """Checks a chunk table's element sizes (and those of ``fields``, where the call has them);
+    returns n, the chains its index of n + 1 entries holds."""
+    if chunk_addr.element_size() != 8 or chunk_len.element_size() != 4 \
+            or chunk_index.element_size() != 8 or (fields is not None and fields.element_size() != 8):
+        wide = "chunk_addr/chunk_index" + ("" if fields is None else "/fields")
+        raise ValueError(f"{wide} must be 64-bit, chunk_len 32-bit")
+    n = chunk_index.numel() - 1
+    if n < 0:
+        raise ValueError("chunk_index must hold n+1 entries")
+    return n
+
+
+def _states_ptr(states, n: int):
+    """The pointer to a chained batch's n states (None for no states)."""
+    if states is None:
+        return None
+    _require_device(states, "states")
+    if states.numel() < n or states.element_size() != 4:
+        raise ValueError("states must hold n 32-bit entries")
+    return states.data_ptr() or None
+
+
+def _non_null_chunk_table(chunk_addr, chunk_len, empty: bool):
+    """The chunk table as the C-ABI wants it, non-null: with no chunk at all (`empty`: pure ACKs,
+    FIN-only bursts, empty datagrams) and a null table, a stand-in of one entry, which the caller
+    gives to ``record_stream`` after the launch (the allocator must not reuse it before)."""
+    if empty and (chunk_addr.data_ptr() == 0 or chunk_len.data_ptr() == 0):
+        torch = _torch()
+        chunk_addr = torch.zeros(1, dtype=torch.int64, device=chunk_addr.device)
+        chunk_len = torch.zeros(1, dtype=torch.int32, device=chunk_addr.device)
+    return chunk_addr, chunk_len
+
+
 def chksum_batch_chain(chunk_addr, chunk_len, chunk_index, states=None, *, out=None,
                        final: bool = False, stream=None, just_written: bool = False):
     """Chained (scatter-gather) batch on the GPU: chain i = chunks
@@ -455,21 +490,11 @@ def chksum_batch_chain(chunk_addr, chunk_len, chunk_index, states=None, *, out=N
     for t, name in ((chunk_addr, "chunk_addr"), (chunk_len, "chunk_len"),
                     (chunk_index, "chunk_index")):
         _require_device(t, name)
-    if chunk_addr.element_size() != 8 or chunk_len.element_size() != 4 \
-            or chunk_index.element_size() != 8:
-        raise ValueError("chunk_addr/chunk_index must be 64-bit, chunk_len 32-bit")
-    n = chunk_index.numel() - 1
-    if n < 0:
-        raise ValueError("chunk_index must hold n+1 entries")
-    sp = 0
-    if states is not None:
-        _require_device(states, "states")
-        if states.numel() < n or states.element_size() != 4:
-            raise ValueError("states must hold n 32-bit entries")
-        sp = states.data_ptr()
+    n = _chunk_table_count(chunk_addr, chunk_len, chunk_index)
+    sp = _states_ptr(states, n)
     out = _out_tensor(out, n, chunk_index)
     st = _lib.load().aipstack_chksum_batch_chain(
-        chunk_addr.data_ptr(), chunk_len.data_ptr(), chunk_index.data_ptr(), sp or None, n,
+        chunk_addr.data_ptr(), chunk_len.data_ptr(), chunk_index.data_ptr(), sp, n,
         out.data_ptr(),
         (AIPSTACK_CHKSUM_FINAL if final else 0) | (AIPSTACK_CHKSUM_JUST_WRITTEN if just_written else 0),
         _stream_handle(stream, chunk_index))
@@ -489,23 +514,13 @@ def chksum_chain_fill(chunk_addr, chunk_len, chunk_index, states, fields, *, out
     for t, name in ((chunk_addr, "chunk_addr"), (chunk_len, "chunk_len"),
                     (chunk_index, "chunk_index"), (fields, "fields")):
         _require_device(t, name)
-    if chunk_addr.element_size() != 8 or chunk_len.element_size() != 4 \
-            or chunk_index.element_size() != 8 or fields.element_size() != 8:
-        raise ValueError("chunk_addr/chunk_index/fields must be 64-bit, chunk_len 32-bit")
-    n = chunk_index.numel() - 1
-    if n < 0:
-        raise ValueError("chunk_index must hold n+1 entries")
+    n = _chunk_table_count(chunk_addr, chunk_len, chunk_index, fields)
     if fields.numel() < n:
         raise ValueError("fields must hold n entries")
-    sp = 0
-    if states is not None:
-        _require_device(states, "states")
-        if states.numel() < n or states.element_size() != 4:
-            raise ValueError("states must hold n 32-bit entries")
-        sp = states.data_ptr()
+    sp = _states_ptr(states, n)
     out = _out_tensor(out, n, chunk_index)
     st = _lib.load().aipstack_chksum_batch_chain_fill(
-        chunk_addr.data_ptr(), chunk_len.data_ptr(), chunk_index.data_ptr(), sp or None,
+        chunk_addr.data_ptr(), chunk_len.data_ptr(), chunk_index.data_ptr(), sp,
         fields.data_ptr(), n, out.data_ptr(),
         (AIPSTACK_CHKSUM_ZERO_AS_FFFF if zero_as_ffff else 0) |
         (AIPSTACK_CHKSUM_JUST_WRITTEN if just_written else 0),
@@ -627,14 +642,9 @@ def tx_fill_header_split(headers, hdr_stride: int, hdr_lens, chunk_addr, chunk_l
                     (chunk_len, "chunk_len"), (chunk_index, "chunk_index")):
         _require_device(t, name)
         _same_device(headers, t, f"headers and {name}")
-    if chunk_addr.element_size() != 8 or chunk_len.element_size() != 4 \
-            or chunk_index.element_size() != 8:
-        raise ValueError("chunk_addr/chunk_index must be 64-bit, chunk_len 32-bit")
+    n = _chunk_table_count(chunk_addr, chunk_len, chunk_index)
     if hdr_lens.dtype not in (torch.int32, torch.uint32):
         raise ValueError("hdr_lens must be an int32/uint32 device tensor")
-    n = chunk_index.numel() - 1
-    if n < 0:
-        raise ValueError("chunk_index must hold n+1 entries")
     if hdr_lens.numel() < n:
         raise ValueError("hdr_lens must hold n entries")
     if hdr_stride <= 0 or n * hdr_stride > headers.numel() * headers.element_size():
@@ -644,13 +654,11 @@ def tx_fill_header_split(headers, hdr_stride: int, hdr_lens, chunk_addr, chunk_l
     out = _u8_out(out, n, headers)
     if n == 0:
         return out
-    if chunk_addr.numel() == 0:  # no chunk at all (pure ACKs): the C-ABI wants non-null tables
-        chunk_addr = torch.zeros(1, dtype=torch.int64, device=headers.device)
-        chunk_len = torch.zeros(1, dtype=torch.int32, device=headers.device)
     lib = _lib.load()
     need = int(lib.aipstack_chksum_tx_fill_hsplit_workspace_bytes(n))
     workspace, ws_bytes = _workspace(workspace, need, headers, "headers")
     launch_stream = _launch_stream(stream, headers.device)
+    chunk_addr, chunk_len = _non_null_chunk_table(chunk_addr, chunk_len, chunk_addr.numel() == 0)
     _check(lib.aipstack_chksum_tx_fill_hsplit(
         headers.data_ptr(), hdr_stride, hdr_lens.data_ptr(), chunk_addr.data_ptr(),
         chunk_len.data_ptr(), chunk_index.data_ptr(), n, out.data_ptr(), workspace.data_ptr(),
@@ -661,6 +669,132 @@ def tx_fill_header_split(headers, hdr_stride: int, hdr_lens, chunk_addr, chunk_l
     for t in (workspace, chunk_addr, chunk_len):
         t.record_stream(launch_stream)
     return out
+
+
+# What differs between the two Tx producers for _tx_produce. min_hdr: the longest header, the
+# least hdr_stride. descs, index, count, owners: the caller's names, for the messages.
+# workspace_bytes(lib, n_owners, n). outs: the tensors of an `out=` result (attribute, its name,
+# element size, which of (n, n_chunks, n + 1, n_owners) it holds at least). owner_status: the
+# result's per-owner status, for a producer that writes one and hdr_lens (UDP).
+_TxProducer = collections.namedtuple(
+    "_TxProducer", "entry dtype min_hdr result descs index count owners workspace_bytes outs "
+    "owner_status", defaults=(None,))
+_TX_OUTS = (("chunk_addr", "out.chunk_addr", 8, 1), ("chunk_len", "out.chunk_len", 4, 1),
+            ("chunk_index", "out.chunk_index", 8, 2), ("status", "out.status", 1, 0))
+
+
+def _tx_produce(p, descs, index, chunk_base, n, n_chunks, *, hdr_stride, headers, just_written,
+                stream, workspace, out, device):
+    """What :func:`tcp_tx_segment` and :func:`udp_tx_fragment` share: the entry point of the
+    :class:`_TxProducer` `p` on the owners `descs` (host arrays, uploaded on the launch stream, or
+    device tensors) with their running sums `index` and `chunk_base`, into `out` or a fresh
+    result of ``p.result``."""
+    torch = _torch()
+    size = p.dtype.itemsize
+    if hasattr(index, "data_ptr"):
+        if n is None or n_chunks is None:
+            raise ValueError(f"device {p.index}/chunk_base need {p.count} and n_chunks")
+        _require_device(descs, p.descs)
+        _require_device(index, p.index)
+        _require_device(chunk_base, "chunk_base")
+        if index.element_size() != 8 or chunk_base.element_size() != 8:
+            raise ValueError(f"{p.index}/chunk_base must be 64-bit")
+        if index.numel() != chunk_base.numel() or index.numel() < 1:
+            raise ValueError(f"{p.index} and chunk_base must hold {p.owners} + 1 entries each")
+        n_owners = index.numel() - 1
+        if descs.numel() * descs.element_size() < size * n_owners:
+            raise ValueError(f"{p.descs} must hold {p.owners} descriptors of {size} bytes")
+        d_descs, d_index, d_base = descs, index, chunk_base
+        dev = descs.device
+    else:
+        g = np.ascontiguousarray(descs, dtype=p.dtype).reshape(-1)
+        ix = np.array(index, dtype=np.uint64).reshape(-1)   # (copies: torch wants them writable)
+        cb = np.array(chunk_base, dtype=np.uint64).reshape(-1)
+        if ix.size != g.size + 1 or cb.size != g.size + 1:
+            raise ValueError(f"{p.index} and chunk_base must hold len({p.descs}) + 1 entries each")
+        n_owners = g.size
+        n = int(ix[-1]) if n is None else n
+        n_chunks = int(cb[-1]) if n_chunks is None else n_chunks
+        if out is not None:
+            dev = out.headers.device
+        elif headers is not None:
+            dev = headers.device
+        else:
+            dev = torch.device("cuda" if device is None else device)
+        raw = np.zeros(max(g.size, 1) * size, dtype=np.uint8)
+        raw[:g.size * size] = g.view(np.uint8)
+        with torch.cuda.stream(_launch_stream(stream, dev)):  # uploads ordered before the call
+            d_descs = torch.from_numpy(raw).to(dev)
+            d_index = torch.from_numpy(ix.view(np.int64)).to(dev)
+            d_base = torch.from_numpy(cb.view(np.int64)).to(dev)
+    n, nc = int(n), int(n_chunks)
+    if n < 0 or nc < 0:
+        raise ValueError(f"{p.count} and n_chunks must not be negative")
+    udp = p.owner_status is not None  # the producer writes hdr_lens and a per-owner status
+    if out is not None:
+        headers, hdr_stride = out.headers, out.hdr_stride
+        least = (n, nc, n + 1, n_owners)
+        for attr, name, esize, which in p.outs:
+            t = getattr(out, attr)
+            _require_device(t, name)
+            if t.element_size() != esize or t.numel() < least[which]:
+                raise ValueError(f"{name} is too small or of the wrong element size")
+        if out.chunk_index.numel() != n + 1 or out.status.numel() != n \
+                or (udp and out.hdr_lens.numel() != n):
+            raise ValueError("out.chunk_index must hold n + 1 entries, out.status"
+                             + (" and out.hdr_lens" if udp else "") + " n")
+    if hdr_stride < p.min_hdr:
+        raise ValueError(f"hdr_stride must be at least {p.min_hdr}")
+    if headers is None:
+        headers = torch.zeros(max(n * hdr_stride, 1), dtype=torch.uint8, device=dev)
+    else:
+        _require_device(headers, "headers")
+        if headers.element_size() != 1 or headers.numel() < n * hdr_stride:
+            raise ValueError("headers must be a uint8 tensor of n whole slots of hdr_stride bytes")
+    if headers.device != d_descs.device:
+        raise ValueError(f"headers and {p.descs} must be on the same device")
+    res = out
+    if out is None:
+        def zeros(cnt, dt):  # (storage of 1 entry at least: the C-ABI wants non-null arrays)
+            return torch.zeros(max(cnt, 1), dtype=dt, device=dev)[:cnt]
+        tables = (zeros(nc, torch.int64), zeros(nc, torch.int32),
+                  torch.zeros(n + 1, dtype=torch.int64, device=dev),
+                  torch.empty(n, dtype=torch.uint8, device=dev))
+        if udp:
+            res = p.result(headers, hdr_stride, zeros(n, torch.int32), *tables,
+                           zeros(n_owners, torch.uint8))
+        else:
+            res = p.result(headers, hdr_stride, *tables)
+    if n == 0:
+        return res
+    lib = _lib.load()
+    workspace, ws_bytes = _workspace(workspace, int(p.workspace_bytes(lib, n_owners, n)), headers,
+                                     "headers")
+    launch_stream = _launch_stream(stream, dev)
+    ca, cl = _non_null_chunk_table(res.chunk_addr, res.chunk_len, nc == 0)
+    flags = AIPSTACK_CHKSUM_JUST_WRITTEN if just_written else 0
+    fn = getattr(lib, p.entry)
+    if udp:
+        os_ = getattr(res, p.owner_status)
+        if n_owners == 0 and os_.data_ptr() == 0:  # no owner: a non-null array all the same
+            os_ = torch.zeros(1, dtype=torch.uint8, device=dev)
+        st = fn(d_descs.data_ptr(), d_index.data_ptr(), d_base.data_ptr(), n_owners, n, nc,
+                headers.data_ptr(), hdr_stride, res.hdr_lens.data_ptr(), ca.data_ptr(),
+                cl.data_ptr(), res.chunk_index.data_ptr(), res.status.data_ptr(), os_.data_ptr(),
+                workspace.data_ptr(), ws_bytes, flags, _stream_handle(launch_stream))
+    else:
+        st = fn(d_descs.data_ptr(), d_index.data_ptr(), d_base.data_ptr(), n_owners, n, nc,
+                headers.data_ptr(), hdr_stride, ca.data_ptr(), cl.data_ptr(),
+                res.chunk_index.data_ptr(), res.status.data_ptr(), workspace.data_ptr(), ws_bytes,
+                flags, _stream_handle(launch_stream))
+    _check(st, p.entry)
+    # the allocator must not reuse the workspace, the uploaded descriptors or a stand-in array
+    # before the launch stream has passed the call
+    for t in (workspace, d_descs, d_index, d_base, ca, cl):
+        t.record_stream(launch_stream)
+    if udp:
+        os_.record_stream(launch_stream)
+    return res
 
 
 AIPSTACK_TCP_SEGMENT_HEADER = 54   # Ethernet 14 + IPv4 20 + TCP 20
@@ -737,94 +871,16 @@ def tcp_tx_segment(bursts, seg_index, chunk_base, *, hdr_stride: int = 64, heade
     at least ``aipstack_tcp_tx_segment_workspace_bytes(n)`` bytes, 8-byte aligned.
     ``just_written``: the AIPSTACK_CHKSUM_JUST_WRITTEN hint for the data read. Status per
     segment: ``AIPSTACK_RX_ACCEPT``, or ``AIPSTACK_TX_BURST_INVALID`` (slot untouched)."""
-    torch = _torch()
-    if hasattr(seg_index, "data_ptr"):
-        if n_segments is None or n_chunks is None:
-            raise ValueError("device seg_index/chunk_base need n_segments and n_chunks")
-        for t, name in ((bursts, "bursts"), (seg_index, "seg_index"), (chunk_base, "chunk_base")):
-            _require_device(t, name)
-        if seg_index.element_size() != 8 or chunk_base.element_size() != 8:
-            raise ValueError("seg_index/chunk_base must be 64-bit")
-        if seg_index.numel() != chunk_base.numel() or seg_index.numel() < 1:
-            raise ValueError("seg_index and chunk_base must hold n_bursts + 1 entries each")
-        n_bursts = seg_index.numel() - 1
-        if bursts.numel() * bursts.element_size() < 96 * n_bursts:
-            raise ValueError("bursts must hold n_bursts descriptors of 96 bytes")
-        d_bursts, d_seg, d_base = bursts, seg_index, chunk_base
-        dev = bursts.device
-    else:
-        b = np.ascontiguousarray(bursts, dtype=TCP_BURST_DTYPE).reshape(-1)
-        si = np.array(seg_index, dtype=np.uint64).reshape(-1)    # (copies: torch wants them writable)
-        cb = np.array(chunk_base, dtype=np.uint64).reshape(-1)
-        if si.size != b.size + 1 or cb.size != b.size + 1:
-            raise ValueError("seg_index and chunk_base must hold len(bursts) + 1 entries each")
-        n_bursts = b.size
-        n_segments = int(si[-1]) if n_segments is None else n_segments
-        n_chunks = int(cb[-1]) if n_chunks is None else n_chunks
-        if out is not None:
-            dev = out.headers.device
-        elif headers is not None:
-            dev = headers.device
-        else:
-            dev = torch.device("cuda" if device is None else device)
-        raw = np.zeros(max(b.size, 1) * 96, dtype=np.uint8)
-        raw[:b.size * 96] = b.view(np.uint8)
-        with torch.cuda.stream(_launch_stream(stream, dev)):  # uploads ordered before the call
-            d_bursts = torch.from_numpy(raw).to(dev)
-            d_seg = torch.from_numpy(si.view(np.int64)).to(dev)
-            d_base = torch.from_numpy(cb.view(np.int64)).to(dev)
-    n, nc = int(n_segments), int(n_chunks)
-    if n < 0 or nc < 0:
-        raise ValueError("n_segments and n_chunks must not be negative")
-    if out is not None:
-        headers, hdr_stride = out.headers, out.hdr_stride
-        for t, name, cnt, size in ((out.chunk_addr, "chunk_addr", nc, 8),
-                                   (out.chunk_len, "chunk_len", nc, 4),
-                                   (out.chunk_index, "chunk_index", n + 1, 8),
-                                   (out.status, "status", n, 1)):
-            _require_device(t, f"out.{name}")
-            if t.element_size() != size or t.numel() < cnt:
-                raise ValueError(f"out.{name} is too small or of the wrong element size")
-        if out.chunk_index.numel() != n + 1 or out.status.numel() != n:
-            raise ValueError("out.chunk_index / out.status must hold n + 1 / n entries")
-        res = out
-    if hdr_stride < AIPSTACK_TCP_SEGMENT_HEADER:
-        raise ValueError("hdr_stride must be at least 54")
-    if headers is None:
-        headers = torch.zeros(max(n * hdr_stride, 1), dtype=torch.uint8, device=dev)
-    else:
-        _require_device(headers, "headers")
-        if headers.element_size() != 1 or headers.numel() < n * hdr_stride:
-            raise ValueError("headers must be a uint8 tensor of n whole slots of hdr_stride bytes")
-    _same_device(headers, d_bursts, "headers and bursts")
-    if out is None:
-        res = TcpSegments(headers, hdr_stride,
-                          torch.zeros(max(nc, 1), dtype=torch.int64, device=dev)[:nc],
-                          torch.zeros(max(nc, 1), dtype=torch.int32, device=dev)[:nc],
-                          torch.zeros(n + 1, dtype=torch.int64, device=dev),
-                          torch.empty(n, dtype=torch.uint8, device=dev))
-    if n == 0:
-        return res
-    lib = _lib.load()
-    need = int(lib.aipstack_tcp_tx_segment_workspace_bytes(n))
-    workspace, ws_bytes = _workspace(workspace, need, headers, "headers")
-    launch_stream = _launch_stream(stream, dev)
-    # no chunk at all (FIN-only bursts): the C-ABI wants non-null tables (storage of 1 entry)
-    ca, cl = res.chunk_addr, res.chunk_len
-    if nc == 0 and (ca.data_ptr() == 0 or cl.data_ptr() == 0):
-        ca = torch.zeros(1, dtype=torch.int64, device=dev)
-        cl = torch.zeros(1, dtype=torch.int32, device=dev)
-    _check(lib.aipstack_tcp_tx_segment(
-        d_bursts.data_ptr(), d_seg.data_ptr(), d_base.data_ptr(), n_bursts, n, nc,
-        headers.data_ptr(), hdr_stride, ca.data_ptr(), cl.data_ptr(), res.chunk_index.data_ptr(),
-        res.status.data_ptr(), workspace.data_ptr(), ws_bytes,
-        AIPSTACK_CHKSUM_JUST_WRITTEN if just_written else 0, _stream_handle(launch_stream)),
-        "aipstack_tcp_tx_segment")
-    # the allocator must not reuse the workspace or the uploaded descriptors before the launch
-    # stream has passed the call
-    for t in (workspace, d_bursts, d_seg, d_base, ca, cl):
-        t.record_stream(launch_stream)
-    return res
+    return _tx_produce(_TCP_SEGMENTS, bursts, seg_index, chunk_base, n_segments, n_chunks,
+                       hdr_stride=hdr_stride, headers=headers, just_written=just_written,
+                       stream=stream, workspace=workspace, out=out, device=device)
+
+
+_TCP_SEGMENTS = _TxProducer(
+    entry="aipstack_tcp_tx_segment", dtype=TCP_BURST_DTYPE, min_hdr=AIPSTACK_TCP_SEGMENT_HEADER,
+    result=TcpSegments, descs="bursts", index="seg_index", count="n_segments", owners="n_bursts",
+    outs=_TX_OUTS,
+    workspace_bytes=lambda lib, n_bursts, n: lib.aipstack_tcp_tx_segment_workspace_bytes(n))
 
 
 AIPSTACK_UDP_FIRST_FRAGMENT_HEADER = 42   # Ethernet 14 + IPv4 20 + UDP 8
@@ -903,100 +959,17 @@ def udp_tx_fragment(dgrams, frag_index, chunk_base, *, hdr_stride: int = 64, hea
     fragment: ``AIPSTACK_RX_ACCEPT``, or ``AIPSTACK_TX_DGRAM_INVALID`` (slot untouched); per
     datagram also ``AIPSTACK_TX_FRAG_NEEDED``. With no fragment at all nothing runs and
     ``dgram_status`` is not written (:func:`udp_dgram_layout` has it)."""
-    torch = _torch()
-    if hasattr(frag_index, "data_ptr"):
-        if n_frags is None or n_chunks is None:
-            raise ValueError("device frag_index/chunk_base need n_frags and n_chunks")
-        for t, name in ((dgrams, "dgrams"), (frag_index, "frag_index"), (chunk_base, "chunk_base")):
-            _require_device(t, name)
-        if frag_index.element_size() != 8 or chunk_base.element_size() != 8:
-            raise ValueError("frag_index/chunk_base must be 64-bit")
-        if frag_index.numel() != chunk_base.numel() or frag_index.numel() < 1:
-            raise ValueError("frag_index and chunk_base must hold n_dgrams + 1 entries each")
-        n_dgrams = frag_index.numel() - 1
-        if dgrams.numel() * dgrams.element_size() < 80 * n_dgrams:
-            raise ValueError("dgrams must hold n_dgrams descriptors of 80 bytes")
-        d_dgrams, d_frag, d_base = dgrams, frag_index, chunk_base
-        dev = dgrams.device
-    else:
-        g = np.ascontiguousarray(dgrams, dtype=UDP_DGRAM_DTYPE).reshape(-1)
-        fi = np.array(frag_index, dtype=np.uint64).reshape(-1)   # (copies: torch wants them writable)
-        cb = np.array(chunk_base, dtype=np.uint64).reshape(-1)
-        if fi.size != g.size + 1 or cb.size != g.size + 1:
-            raise ValueError("frag_index and chunk_base must hold len(dgrams) + 1 entries each")
-        n_dgrams = g.size
-        n_frags = int(fi[-1]) if n_frags is None else n_frags
-        n_chunks = int(cb[-1]) if n_chunks is None else n_chunks
-        if out is not None:
-            dev = out.headers.device
-        elif headers is not None:
-            dev = headers.device
-        else:
-            dev = torch.device("cuda" if device is None else device)
-        raw = np.zeros(max(g.size, 1) * 80, dtype=np.uint8)
-        raw[:g.size * 80] = g.view(np.uint8)
-        with torch.cuda.stream(_launch_stream(stream, dev)):  # uploads ordered before the call
-            d_dgrams = torch.from_numpy(raw).to(dev)
-            d_frag = torch.from_numpy(fi.view(np.int64)).to(dev)
-            d_base = torch.from_numpy(cb.view(np.int64)).to(dev)
-    n, nc = int(n_frags), int(n_chunks)
-    if n < 0 or nc < 0:
-        raise ValueError("n_frags and n_chunks must not be negative")
-    if out is not None:
-        headers, hdr_stride = out.headers, out.hdr_stride
-        for t, name, cnt, size in ((out.hdr_lens, "hdr_lens", n, 4),
-                                   (out.chunk_addr, "chunk_addr", nc, 8),
-                                   (out.chunk_len, "chunk_len", nc, 4),
-                                   (out.chunk_index, "chunk_index", n + 1, 8),
-                                   (out.status, "status", n, 1),
-                                   (out.dgram_status, "dgram_status", n_dgrams, 1)):
-            _require_device(t, f"out.{name}")
-            if t.element_size() != size or t.numel() < cnt:
-                raise ValueError(f"out.{name} is too small or of the wrong element size")
-        if out.chunk_index.numel() != n + 1 or out.status.numel() != n or out.hdr_lens.numel() != n:
-            raise ValueError("out.chunk_index / out.status / out.hdr_lens must hold n + 1 / n / n entries")
-        res = out
-    if hdr_stride < AIPSTACK_UDP_FIRST_FRAGMENT_HEADER:
-        raise ValueError("hdr_stride must be at least 42")
-    if headers is None:
-        headers = torch.zeros(max(n * hdr_stride, 1), dtype=torch.uint8, device=dev)
-    else:
-        _require_device(headers, "headers")
-        if headers.element_size() != 1 or headers.numel() < n * hdr_stride:
-            raise ValueError("headers must be a uint8 tensor of n whole slots of hdr_stride bytes")
-    _same_device(headers, d_dgrams, "headers and dgrams")
-    if out is None:
-        res = UdpFragments(headers, hdr_stride,
-                           torch.zeros(max(n, 1), dtype=torch.int32, device=dev)[:n],
-                           torch.zeros(max(nc, 1), dtype=torch.int64, device=dev)[:nc],
-                           torch.zeros(max(nc, 1), dtype=torch.int32, device=dev)[:nc],
-                           torch.zeros(n + 1, dtype=torch.int64, device=dev),
-                           torch.empty(n, dtype=torch.uint8, device=dev),
-                           torch.zeros(max(n_dgrams, 1), dtype=torch.uint8, device=dev)[:n_dgrams])
-    if n == 0:
-        return res
-    lib = _lib.load()
-    need = int(lib.aipstack_udp_tx_fragment_workspace_bytes(n_dgrams, n))
-    workspace, ws_bytes = _workspace(workspace, need, headers, "headers")
-    launch_stream = _launch_stream(stream, dev)
-    # no chunk at all (empty datagrams) or no datagram: the C-ABI wants non-null arrays
-    ca, cl, ds = res.chunk_addr, res.chunk_len, res.dgram_status
-    if nc == 0 and (ca.data_ptr() == 0 or cl.data_ptr() == 0):
-        ca = torch.zeros(1, dtype=torch.int64, device=dev)
-        cl = torch.zeros(1, dtype=torch.int32, device=dev)
-    if n_dgrams == 0 and ds.data_ptr() == 0:
-        ds = torch.zeros(1, dtype=torch.uint8, device=dev)
-    _check(lib.aipstack_udp_tx_fragment(
-        d_dgrams.data_ptr(), d_frag.data_ptr(), d_base.data_ptr(), n_dgrams, n, nc,
-        headers.data_ptr(), hdr_stride, res.hdr_lens.data_ptr(), ca.data_ptr(), cl.data_ptr(),
-        res.chunk_index.data_ptr(), res.status.data_ptr(), ds.data_ptr(), workspace.data_ptr(),
-        ws_bytes, AIPSTACK_CHKSUM_JUST_WRITTEN if just_written else 0,
-        _stream_handle(launch_stream)), "aipstack_udp_tx_fragment")
-    # the allocator must not reuse the workspace or the uploaded descriptors before the launch
-    # stream has passed the call
-    for t in (workspace, d_dgrams, d_frag, d_base, ca, cl, ds):
-        t.record_stream(launch_stream)
-    return res
+    return _tx_produce(_UDP_FRAGMENTS, dgrams, frag_index, chunk_base, n_frags, n_chunks,
+                       hdr_stride=hdr_stride, headers=headers, just_written=just_written,
+                       stream=stream, workspace=workspace, out=out, device=device)
+
+
+_UDP_FRAGMENTS = _TxProducer(
+    entry="aipstack_udp_tx_fragment", dtype=UDP_DGRAM_DTYPE,
+    min_hdr=AIPSTACK_UDP_FIRST_FRAGMENT_HEADER, result=UdpFragments, descs="dgrams",
+    index="frag_index", count="n_frags", owners="n_dgrams", owner_status="dgram_status",
+    outs=_TX_OUTS + (("hdr_lens", "out.hdr_lens", 4, 0), ("dgram_status", "out.dgram_status", 1, 3)),
+    workspace_bytes=lambda lib, n_dgrams, n: lib.aipstack_udp_tx_fragment_workspace_bytes(n_dgrams, n))
 
 
 AIPSTACK_RX_DROP_TCP_OFFSET = 11    # tcp_rx_parse: TCP checksum good, data offset out of range
@@ -1304,14 +1277,9 @@ def _linearise_call(name, where, segments, headers, hdr_stride, hdr_lens, chunk_
     if not (frames.is_cuda or frames.is_pinned()) or not frames.is_contiguous() \
             or frames.element_size() != 1:
         raise ValueError("frames must be a contiguous uint8 tensor in device or pinned host memory")
-    if chunk_addr.element_size() != 8 or chunk_len.element_size() != 4 \
-            or chunk_index.element_size() != 8:
-        raise ValueError("chunk_addr/chunk_index must be 64-bit, chunk_len 32-bit")
+    n = _chunk_table_count(chunk_addr, chunk_len, chunk_index)
     if hdr_lens.dtype not in (torch.int32, torch.uint32):
         raise ValueError("hdr_lens must be an int32/uint32 device tensor")
-    n = chunk_index.numel() - 1
-    if n < 0:
-        raise ValueError("chunk_index must hold n+1 entries")
     if hdr_lens.numel() < n or (seg_status is not None and
                                 (seg_status.numel() < n or seg_status.element_size() != 1)):
         raise ValueError("hdr_lens and seg_status (uint8) must hold n entries")
@@ -1338,21 +1306,18 @@ def _linearise_call(name, where, segments, headers, hdr_stride, hdr_lens, chunk_
             raise ValueError("lens must be an int32/uint32 device tensor with >= n elements")
     status = _u8_out(status, n, headers)
     if n:
-        stand_in = chunk_addr.numel() == 0
-        if stand_in:  # no chunk at all (pure ACKs): the C-ABI wants non-null tables
-            chunk_addr = torch.zeros(1, dtype=torch.int64, device=headers.device)
-            chunk_len = torch.zeros(1, dtype=torch.int32, device=headers.device)
         launch_stream = _launch_stream(stream, headers.device)
+        ca, cl = _non_null_chunk_table(chunk_addr, chunk_len, chunk_addr.numel() == 0)
         _check(getattr(_lib.load(), name)(
-            headers.data_ptr(), hdr_stride, hdr_lens.data_ptr(), chunk_addr.data_ptr(),
-            chunk_len.data_ptr(), chunk_index.data_ptr(), n,
+            headers.data_ptr(), hdr_stride, hdr_lens.data_ptr(), ca.data_ptr(), cl.data_ptr(),
+            chunk_index.data_ptr(), n,
             seg_status.data_ptr() if seg_status is not None else None, frames.data_ptr(), *place,
             int(frame_max), lens.data_ptr(), status.data_ptr(),
             AIPSTACK_CHKSUM_JUST_WRITTEN if just_written else 0, _stream_handle(launch_stream)),
             name)
-        if stand_in:  # the allocator must not reuse the stand-in table before the launch is done
-            chunk_addr.record_stream(launch_stream)
-            chunk_len.record_stream(launch_stream)
+        if ca is not chunk_addr:  # the allocator must not reuse a stand-in before the launch is done
+            ca.record_stream(launch_stream)
+            cl.record_stream(launch_stream)
     return LinearFrames(frames, arg if kind == "slots" else None,
                         arg if kind != "slots" else None, lens, status)
 

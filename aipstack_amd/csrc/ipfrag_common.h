@@ -7,6 +7,7 @@
 #include <cstdint>
 
 #include "aipstack_amd/chksum.h"
+#include "tx_producer_common.h"
 
 #if defined(__HIPCC__)
 #define AIPSTACK_IPFRAG_HD __host__ __device__ inline
@@ -15,8 +16,6 @@
 #endif
 
 namespace aipstack_amd {
-
-constexpr uint64_t kIpFragMaxCount = 1ull << 40;  // datagrams, fragments, chunks of one call
 
 // A datagram as sendIp4Dgram / send_fragmented cut it (ip/IpStack.h:404-421, 470-538): the IP
 // payload of P = 8 + D bytes (UDP header and data) in S fragments, every one but the last of

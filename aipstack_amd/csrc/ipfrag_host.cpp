@@ -21,7 +21,7 @@ using namespace aipstack_amd;
 extern "C" int aipstack_udp_dgram_layout(const aipstack_udp_dgram *h_dgrams, uint64_t n_dgrams,
                                          uint64_t *h_frag_index, uint64_t *h_chunk_base,
                                          uint8_t *h_status) {
-    if (!h_frag_index || !h_chunk_base || (n_dgrams != 0 && !h_dgrams) || n_dgrams > kIpFragMaxCount)
+    if (!h_frag_index || !h_chunk_base || (n_dgrams != 0 && !h_dgrams) || n_dgrams > kTxMaxCount)
         return AIPSTACK_CHKSUM_EINVAL;
     uint64_t frags = 0, chunks = 0;
     h_frag_index[0] = 0;
@@ -40,8 +40,8 @@ extern "C" int aipstack_udp_dgram_layout(const aipstack_udp_dgram *h_dgrams, uin
 }
 
 extern "C" uint64_t aipstack_udp_tx_fragment_workspace_bytes(uint64_t n_dgrams, uint64_t n_frags) {
-    if (n_dgrams > kIpFragMaxCount) n_dgrams = kIpFragMaxCount;
-    if (n_frags > kIpFragMaxCount) n_frags = kIpFragMaxCount;
+    if (n_dgrams > kTxMaxCount) n_dgrams = kTxMaxCount;
+    if (n_frags > kTxMaxCount) n_frags = kTxMaxCount;
     return udp_frag_workspace(n_dgrams, n_frags).bytes;
 }
 
@@ -54,16 +54,12 @@ int udp_tx_fragment_check_args(const void *d_dgrams, const void *d_frag_index,
                                const void *d_chunk_len, const void *d_chunk_index,
                                const void *d_status, const void *d_dgram_status,
                                const void *d_workspace, uint64_t workspace_bytes) {
-    if (!d_dgrams || !d_frag_index || !d_chunk_base || !d_hdr || !d_hdr_len || !d_chunk_addr ||
-        !d_chunk_len || !d_chunk_index || !d_status || !d_dgram_status || !d_workspace)
-        return AIPSTACK_CHKSUM_EINVAL;
-    if (hdr_stride < AIPSTACK_UDP_FIRST_FRAGMENT_HEADER || n_frags > kIpFragMaxCount ||
-        n_chunks > kIpFragMaxCount || n_dgrams > kIpFragMaxCount)
-        return AIPSTACK_CHKSUM_EINVAL;
-    if (workspace_bytes < aipstack_udp_tx_fragment_workspace_bytes(n_dgrams, n_frags) ||
-        ((uintptr_t)d_workspace & 7u) != 0)
-        return AIPSTACK_CHKSUM_EINVAL;
-    return AIPSTACK_CHKSUM_OK;
+    return tx_producer_check_args({d_dgrams, d_frag_index, d_chunk_base, d_hdr, d_hdr_len,
+                                   d_chunk_addr, d_chunk_len, d_chunk_index, d_status,
+                                   d_dgram_status},
+                                  hdr_stride, AIPSTACK_UDP_FIRST_FRAGMENT_HEADER, n_dgrams, n_frags,
+                                  n_chunks, d_workspace, workspace_bytes,
+                                  aipstack_udp_tx_fragment_workspace_bytes(n_dgrams, n_frags));
 }
 
 }  // namespace aipstack_amd

@@ -31,6 +31,10 @@
 // Header words are summed as in tcpseg_kernels.hip: little-endian 16-bit halves of the template's
 // dwords (every field lies at an even offset of the 8-byte aligned template), folded and
 // byte-swapped once, then the per-fragment big-endian words added.
+//
+// tx_producer.h has what this file shares with tcpseg_kernels.hip: the owner search, an owner's
+// ranges and contract, the record, the template loader and its sums, and the slot store. Here:
+// what is UDP's own, and the chunk entries written each from its own lane.
 
 #include <hip/hip_runtime.h>
 
@@ -39,76 +43,14 @@
 #include "aipstack_amd/chksum.h"
 #include "chksum_internal.h"
 #include "ipfrag_common.h"
-#include "lane_pass.h"
+#include "tx_producer.h"
 
 namespace aipstack_amd {
 namespace {
 
-// The record of fragment i (workspace, 8 bytes): bits 0-39 the datagram that owns it, 40-55 the
-// IPv4 header checksum, 56 = valid (emit the slot; else status AIPSTACK_TX_DGRAM_INVALID).
-constexpr uint64_t kRecDgramMask = (1ull << 40) - 1u;
-constexpr uint64_t kRecValid = 1ull << 56;
-
-// The first j in [lo, hi] with idx[j] > i (hi if there is none); reads entries in [lo, hi).
-__device__ __forceinline__ uint64_t uf_upper_bound(const uint64_t *__restrict__ idx, uint64_t lo,
-                                                   uint64_t hi, uint64_t i) {
-    while (lo < hi) {
-        const uint64_t mid = lo + ((hi - lo) >> 1);
-        if (idx[mid] <= i) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-
-// One element per lane of the n elements that the running sums `idx` (n_dgrams + 1 entries)
-// share out among the datagrams: owned(d, i) for element i of datagram d (idx[d] <= i <
-// idx[d+1]), unowned(j, i) for one the sums give to no datagram (they do not run from 0 to n; j
-// = where the search ended). The wave's 64 elements mostly share one or two datagrams: the
-// owners of its first and last element are found with wave-uniform searches, and each lane
-// searches only between them (no step at all when they agree: d is then wave-uniform, so that
-// the descriptor and index loads of owned() are shared).
-template <class Owned, class Unowned>
-__device__ __forceinline__ void uf_for_each(const uint64_t *__restrict__ idx, uint64_t n_dgrams,
-                                            uint64_t n, const WaveStride &ws, Owned owned,
-                                            Unowned unowned) {
-    for (uint64_t base = uniform64(ws.first); base < n; base += ws.step) {
-        const uint64_t last = base + (kWave - 1) < n ? base + (kWave - 1) : n - 1;
-        const uint64_t j0 = uniform64(uf_upper_bound(idx, 0, n_dgrams + 1, base));
-        const uint64_t j1 = uniform64(uf_upper_bound(idx, j0, n_dgrams + 1, last));
-        const uint64_t i = base + ws.lane;
-        if (i >= n) continue;
-        if (j0 == j1 && j0 >= 1 && j0 <= n_dgrams) {
-            const uint64_t d = j0 - 1;
-            if (idx[d] <= base && last < idx[d + 1]) {
-                owned(d, i);
-                continue;
-            }
-        }
-        const uint64_t j = uf_upper_bound(idx, j0, j1, i);
-        const bool own = j >= 1 && j <= n_dgrams && idx[j - 1] <= i && i < idx[j];
-        if (own) owned(j - 1, i);
-        else unowned(j, i);
-    }
-}
-
 // The template's first 11 dwords (44 of its 48 bytes; the struct is 8-byte aligned and hdr lies
 // at offset 32).
-struct Template {
-    uint32_t t[11];
-};
-
-__device__ __forceinline__ Template uf_template(const aipstack_udp_dgram *__restrict__ g) {
-    Template r;
-    const uint2 *p = reinterpret_cast<const uint2 *>(g->hdr);
-#pragma unroll
-    for (int q = 0; q < 5; ++q) {
-        const uint2 v = p[q];
-        r.t[2 * q] = v.x;
-        r.t[2 * q + 1] = v.y;
-    }
-    r.t[10] = reinterpret_cast<const uint32_t *>(g->hdr)[10];
-    return r;
-}
+using Template = HeaderWords<11>;
 
 // What changes per fragment (ip/IpStack.h:431-440, 497-509).
 struct FragWords {
@@ -126,42 +68,19 @@ __device__ __forceinline__ FragWords uf_fragment(const aipstack_udp_dgram *__res
     return w;
 }
 
-// Little-endian halves of the source and destination address (frame bytes 26-33).
-__device__ __forceinline__ uint32_t uf_addr_halves(const Template &h) {
-    return (h.t[6] >> 16) + (h.t[7] & 0xFFFFu) + (h.t[7] >> 16) + (h.t[8] & 0xFFFFu);
-}
-
-// The IPv4 header checksum: version/IHL/DSCP, TTL/protocol and the addresses from the template,
-// total length, ident and flags/fragment offset per fragment, the field as 0. Fragment 0 as
-// :425-453 accumulates it, the others as IpChksum over the 20 bytes (:510-515): the same sum.
+// The IPv4 header checksum: what ip_header_checksum takes from the template, and total length,
+// ident and flags/fragment offset per fragment. Fragment 0 as :425-453 accumulates it, the others
+// as IpChksum over the 20 bytes (:510-515): the same sum.
 __device__ __forceinline__ uint32_t uf_ip_checksum(const Template &h, const FragWords &w) {
-    const uint32_t le = (h.t[3] >> 16) + (h.t[5] >> 16) + uf_addr_halves(h);
-    const uint32_t be = bswap16(fold16(le)) + w.total_len + w.ident + w.flags_offset;
-    return ~fold16(be) & 0xFFFFu;
+    return ip_header_checksum(h, 0u, w.total_len + w.ident + w.flags_offset);
 }
 
 // The State the datagram's chain is resumed from (udp/IpUdpProto.h:163-174): the pseudo-header
 // (addresses, protocol 17, P) and the 8 UDP header bytes (ports from the template, length P, the
 // checksum field as 0). 10 words: far below 2^32.
 __device__ __forceinline__ uint32_t uf_udp_seed(const Template &h, uint32_t P) {
-    const uint32_t le = uf_addr_halves(h) + (h.t[8] >> 16) + (h.t[9] & 0xFFFFu);
+    const uint32_t le = addr_halves(h) + (h.t[8] >> 16) + (h.t[9] & 0xFFFFu);
     return bswap16(fold16(le)) + 17u + P + P;
-}
-
-// A datagram's view of the caller's two indices: fragments [fb, fe), chunks [cb, ce).
-struct DgramRange {
-    uint64_t fb, fe, cb, ce;
-};
-
-__device__ __forceinline__ DgramRange uf_range(const uint64_t *__restrict__ frag_index,
-                                               const uint64_t *__restrict__ chunk_base, uint64_t d) {
-    return DgramRange{frag_index[d], frag_index[d + 1], chunk_base[d], chunk_base[d + 1]};
-}
-
-__device__ __forceinline__ bool uf_dgram_ok(const UdpDgramShape &s, const DgramRange &r,
-                                            uint64_t n_frags, uint64_t n_chunks) {
-    return s.valid && r.fe >= r.fb && r.fe - r.fb == s.S && r.fe <= n_frags && r.ce >= r.cb &&
-           r.ce - r.cb == s.C && r.ce <= n_chunks;
 }
 
 __device__ __forceinline__ void uf_put_chunk(uint64_t *__restrict__ chunk_addr,
@@ -183,25 +102,24 @@ __global__ __launch_bounds__(kBlock) void ipfrag_plan_kernel(
         __builtin_nontemporal_store(n_chunks, &chunk_index[n_frags]);
 
     // Fragments: the index entry and the record of fragment i.
-    uf_for_each(
+    for_each_owned(
         frag_index, n_dgrams, n_frags, ws,
         [&](uint64_t d, uint64_t i) {
             const aipstack_udp_dgram *__restrict__ g = dgrams + d;
-            const DgramRange r = uf_range(frag_index, chunk_base, d);
+            const OwnerRange r = owner_range(frag_index, chunk_base, d);
             const UdpDgramShape s = udp_dgram_shape(*g);
-            const uint64_t k = i - r.fb;
-            uint64_t rec = d & kRecDgramMask, ci;
-            if (uf_dgram_ok(s, r, n_frags, n_chunks)) {
-                const Template h = uf_template(g);
+            const uint64_t k = i - r.eb;
+            uint64_t rec = make_record(d, 0, false), ci;
+            if (owner_ok(s.valid, s.S, s.C, r, n_frags, n_chunks)) {
+                const Template h = load_header_words<11>(g->hdr);
                 const FragWords w = uf_fragment(g, h, s, udp_frag_range(s, k), k);
                 ci = r.cb + k + (k > s.straddle ? 1u : 0u);
-                rec |= (uint64_t)uf_ip_checksum(h, w) << 40 | kRecValid;
+                rec = make_record(d, uf_ip_checksum(h, w), true);
             } else {
                 // its chunk entries are written empty; the fragments the index gives it share
                 // them out in order, clipped to the table, so that the index stays in [0, n_chunks]
-                const uint64_t c0 = r.cb < n_chunks ? r.cb : n_chunks;
-                uint64_t cnt = r.ce >= r.cb ? r.ce - r.cb : 0u;
-                if (cnt > n_chunks - c0) cnt = n_chunks - c0;
+                uint64_t c0, cnt;
+                clip_chunks(r, n_chunks, c0, cnt);
                 ci = c0 + (k < cnt ? k : cnt);
             }
             __builtin_nontemporal_store(ci, &chunk_index[i]);
@@ -215,15 +133,15 @@ __global__ __launch_bounds__(kBlock) void ipfrag_plan_kernel(
     // Chunk entries: entry c is entry kc = c - chunk_base[d] of its datagram; fragment k's first
     // entry is k, plus 1 after the straddling fragment, whose two entries are its bytes of piece
     // 0 and of piece 1.
-    uf_for_each(
+    for_each_owned(
         chunk_base, n_dgrams, n_chunks, ws,
         [&](uint64_t d, uint64_t c) {
             const aipstack_udp_dgram *__restrict__ g = dgrams + d;
-            const DgramRange r = uf_range(frag_index, chunk_base, d);
+            const OwnerRange r = owner_range(frag_index, chunk_base, d);
             const UdpDgramShape s = udp_dgram_shape(*g);
             uint64_t addr = 0;
             uint32_t len = 0;
-            if (uf_dgram_ok(s, r, n_frags, n_chunks)) {
+            if (owner_ok(s.valid, s.S, s.C, r, n_frags, n_chunks)) {
                 const uint64_t kc = c - r.cb;  // < C
                 const uint64_t k = kc - (kc > s.straddle ? 1u : 0u);
                 const UdpFragRange f = udp_frag_range(s, k);
@@ -242,13 +160,13 @@ __global__ __launch_bounds__(kBlock) void ipfrag_plan_kernel(
     // Datagrams: status, seed and chain bound.
     for (uint64_t d = (uint64_t)blockIdx.x * kBlock + threadIdx.x; d < n_dgrams; d += ws.step) {
         const aipstack_udp_dgram *__restrict__ g = dgrams + d;
-        const DgramRange r = uf_range(frag_index, chunk_base, d);
+        const OwnerRange r = owner_range(frag_index, chunk_base, d);
         const UdpDgramShape s = udp_dgram_shape(*g);
         uint32_t seed = 0;
         uint8_t st = AIPSTACK_TX_DGRAM_INVALID;
-        if (uf_dgram_ok(s, r, n_frags, n_chunks)) {
+        if (owner_ok(s.valid, s.S, s.C, r, n_frags, n_chunks)) {
             st = (uint8_t)(s.frag_needed ? AIPSTACK_TX_FRAG_NEEDED : AIPSTACK_RX_ACCEPT);
-            seed = uf_udp_seed(uf_template(g), s.P);
+            seed = uf_udp_seed(load_header_words<11>(g->hdr), s.P);
         }
         dgram_status[d] = st;
         __builtin_nontemporal_store(seed, &seeds[d]);
@@ -258,7 +176,7 @@ __global__ __launch_bounds__(kBlock) void ipfrag_plan_kernel(
     }
 }
 
-// Emit pass. LINES: hdr_stride == 64 and the ring starts on a 64-byte boundary.
+// Emit pass. LINES: ring_in_lines(hdr_base, hdr_stride).
 template <bool LINES>
 __global__ __launch_bounds__(kBlock) void ipfrag_emit_kernel(
     const aipstack_udp_dgram *__restrict__ dgrams, const uint64_t *__restrict__ frag_index,
@@ -271,19 +189,19 @@ __global__ __launch_bounds__(kBlock) void ipfrag_emit_kernel(
         const uint64_t i = base + ws.lane;
         const bool active = i < n_frags;
         const uint64_t rec = active ? __builtin_nontemporal_load(&records[i]) : 0u;
-        const bool valid = (rec & kRecValid) != 0u;
+        const bool valid = record_valid(rec);
         uint32_t hl = 0;
         uint32_t o[16];
 #pragma unroll
         for (int q = 0; q < 16; ++q) o[q] = 0u;
         if (valid) {
-            const uint64_t d = rec & kRecDgramMask;
+            const uint64_t d = record_owner(rec);
             const aipstack_udp_dgram *__restrict__ g = dgrams + d;
             const UdpDgramShape s = udp_dgram_shape(*g);
             const uint64_t k = i - frag_index[d];
-            const Template h = uf_template(g);
+            const Template h = load_header_words<11>(g->hdr);
             const FragWords w = uf_fragment(g, h, s, udp_frag_range(s, k), k);
-            const uint32_t ipchk = (uint32_t)(rec >> 40) & 0xFFFFu;
+            const uint32_t ipchk = record_ip_checksum(rec);
 #pragma unroll
             for (int q = 0; q < 8; ++q) o[q] = h.t[q];
             o[4] = bswap16(w.total_len) | bswap16(w.ident) << 16;
@@ -306,24 +224,9 @@ __global__ __launch_bounds__(kBlock) void ipfrag_emit_kernel(
             status[i] = (uint8_t)(valid ? AIPSTACK_RX_ACCEPT : AIPSTACK_TX_DGRAM_INVALID);
             __builtin_nontemporal_store(hl, &hdr_len[i]);
         }
-        if constexpr (LINES) {
-            const uint64_t ok = __builtin_amdgcn_ballot_w64(valid);  // (valid: below n_frags)
-            store_wave_lines<4>(tile[ws.wave], ws.lane, hdr_base, base, ok, o);
-        } else if (valid) {
-            const uint64_t P = hdr_base + i * hdr_stride;
-#pragma unroll
-            for (int q = 0; q < 2; ++q)
-                *reinterpret_cast<global_t<u32x4, 1> *>(P + 16u * q) =
-                    u32x4{o[4 * q], o[4 * q + 1], o[4 * q + 2], o[4 * q + 3]};
-            if (hl == AIPSTACK_UDP_FIRST_FRAGMENT_HEADER) {
-                *reinterpret_cast<global_t<u32x2, 1> *>(P + 32u) = u32x2{o[8], o[9]};
-                *reinterpret_cast<global_t<uint16_t, 1> *>(P + 40u) = (uint16_t)o[10];
-            } else {
-                *reinterpret_cast<global_t<uint16_t, 1> *>(P + 32u) = (uint16_t)o[8];
-            }
-            const uint32_t end = hdr_stride < 64u ? (uint32_t)hdr_stride : 64u;
-            for (uint32_t z = hl; z < end; ++z) *reinterpret_cast<global_t<uint8_t> *>(P + z) = 0u;
-        }
+        store_header_slot<LINES, AIPSTACK_UDP_FIRST_FRAGMENT_HEADER,
+                          AIPSTACK_UDP_NEXT_FRAGMENT_HEADER>(tile, ws, hdr_base, hdr_stride, base,
+                                                             valid, hl, o);
     }
 }
 
@@ -370,13 +273,9 @@ extern "C" int aipstack_udp_tx_fragment(const aipstack_udp_dgram *d_dgrams,
         if (st != AIPSTACK_CHKSUM_OK) return st;
     }
     const uint64_t base = (uint64_t)(uintptr_t)d_hdr;
-    if (hdr_stride == 64u && (base & 63u) == 0u)
-        hipLaunchKernelGGL(ipfrag_emit_kernel<true>, dim3(emit_blocks), dim3(kBlock), 0, s, d_dgrams,
-                           d_frag_index, records, sums, base, hdr_stride, d_hdr_len, d_status,
-                           n_frags);
-    else
-        hipLaunchKernelGGL(ipfrag_emit_kernel<false>, dim3(emit_blocks), dim3(kBlock), 0, s, d_dgrams,
-                           d_frag_index, records, sums, base, hdr_stride, d_hdr_len, d_status,
-                           n_frags);
+    const auto emit = ring_in_lines(base, hdr_stride) ? ipfrag_emit_kernel<true>
+                                                      : ipfrag_emit_kernel<false>;
+    hipLaunchKernelGGL(emit, dim3(emit_blocks), dim3(kBlock), 0, s, d_dgrams, d_frag_index, records,
+                       sums, base, hdr_stride, d_hdr_len, d_status, n_frags);
     return check_hip(hipGetLastError());
 }

@@ -7,6 +7,7 @@
 #include <cstdint>
 
 #include "aipstack_amd/chksum.h"
+#include "tx_producer_common.h"
 
 #if defined(__HIPCC__)
 #define AIPSTACK_TCPSEG_HD __host__ __device__ inline
@@ -15,8 +16,6 @@
 #endif
 
 namespace aipstack_amd {
-
-constexpr uint64_t kTcpSegMaxCount = 1ull << 40;  // segments, chunks, bursts of one call
 
 // A burst as pcb_output_active's loop cuts it (tcp/IpTcpProto_output.h:1069-1090): D data bytes
 // in S segments of mss bytes (the last one shorter), C chunks. The range is two pieces of the

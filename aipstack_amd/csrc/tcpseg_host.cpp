@@ -22,7 +22,7 @@ using namespace aipstack_amd;
 
 extern "C" int aipstack_tcp_burst_layout(const aipstack_tcp_burst *h_bursts, uint64_t n_bursts,
                                          uint64_t *h_seg_index, uint64_t *h_chunk_base) {
-    if (!h_seg_index || !h_chunk_base || (n_bursts != 0 && !h_bursts) || n_bursts > kTcpSegMaxCount)
+    if (!h_seg_index || !h_chunk_base || (n_bursts != 0 && !h_bursts) || n_bursts > kTxMaxCount)
         return AIPSTACK_CHKSUM_EINVAL;
     uint64_t segs = 0, chunks = 0;
     h_seg_index[0] = 0;
@@ -40,7 +40,7 @@ extern "C" int aipstack_tcp_burst_layout(const aipstack_tcp_burst *h_bursts, uin
 
 // Workspace of n segments: records (8n bytes), seeds (4n), chain sums (2n).
 extern "C" uint64_t aipstack_tcp_tx_segment_workspace_bytes(uint64_t n) {
-    if (n > kTcpSegMaxCount) n = kTcpSegMaxCount;
+    if (n > kTxMaxCount) n = kTxMaxCount;
     return (14u * n + 7u) & ~(uint64_t)7;
 }
 
@@ -52,16 +52,11 @@ int tcp_tx_segment_check_args(const void *d_bursts, const void *d_seg_index,
                               const void *d_chunk_addr, const void *d_chunk_len,
                               const void *d_chunk_index, const void *d_status,
                               const void *d_workspace, uint64_t workspace_bytes) {
-    if (!d_bursts || !d_seg_index || !d_chunk_base || !d_hdr || !d_chunk_addr || !d_chunk_len ||
-        !d_chunk_index || !d_status || !d_workspace)
-        return AIPSTACK_CHKSUM_EINVAL;
-    if (hdr_stride < AIPSTACK_TCP_SEGMENT_HEADER || n_segments > kTcpSegMaxCount ||
-        n_chunks > kTcpSegMaxCount || n_bursts > kTcpSegMaxCount)
-        return AIPSTACK_CHKSUM_EINVAL;
-    if (workspace_bytes < aipstack_tcp_tx_segment_workspace_bytes(n_segments) ||
-        ((uintptr_t)d_workspace & 7u) != 0)
-        return AIPSTACK_CHKSUM_EINVAL;
-    return AIPSTACK_CHKSUM_OK;
+    return tx_producer_check_args({d_bursts, d_seg_index, d_chunk_base, d_hdr, d_chunk_addr,
+                                   d_chunk_len, d_chunk_index, d_status},
+                                  hdr_stride, AIPSTACK_TCP_SEGMENT_HEADER, n_bursts, n_segments,
+                                  n_chunks, d_workspace, workspace_bytes,
+                                  aipstack_tcp_tx_segment_workspace_bytes(n_segments));
 }
 
 }  // namespace aipstack_amd

@@ -24,6 +24,10 @@
 // Header words are summed as the repository does everywhere: little-endian 16-bit halves of the
 // template's dwords (every field lies at an even offset of the 8-byte aligned template), folded
 // and byte-swapped once, then the per-segment big-endian words added.
+//
+// tx_producer.h has what this file shares with ipfrag_kernels.hip: the owner search, an owner's
+// ranges and contract, the record, the template loader and its sums, and the slot store. Here:
+// what is TCP's own, and the chunk entries written from the segment lanes.
 
 #include <hip/hip_runtime.h>
 
@@ -31,44 +35,14 @@
 
 #include "aipstack_amd/chksum.h"
 #include "chksum_internal.h"
-#include "lane_pass.h"
 #include "tcpseg_common.h"
+#include "tx_producer.h"
 
 namespace aipstack_amd {
 namespace {
 
-// The record of segment i (workspace, 8 bytes): bits 0-39 the burst that owns it, 40-55 the
-// IPv4 header checksum, 56 = valid (emit the slot; else status AIPSTACK_TX_BURST_INVALID).
-constexpr uint64_t kRecBurstMask = (1ull << 40) - 1u;
-constexpr uint64_t kRecValid = 1ull << 56;
-
-// The first j in [lo, hi] with idx[j] > i (hi if there is none); reads entries in [lo, hi).
-__device__ __forceinline__ uint64_t ts_upper_bound(const uint64_t *__restrict__ idx, uint64_t lo,
-                                                   uint64_t hi, uint64_t i) {
-    while (lo < hi) {
-        const uint64_t mid = lo + ((hi - lo) >> 1);
-        if (idx[mid] <= i) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-
 // The template's 14 dwords (56 bytes; the struct is 8-byte aligned and hdr lies at offset 40).
-struct Template {
-    uint32_t t[14];
-};
-
-__device__ __forceinline__ Template ts_template(const aipstack_tcp_burst *__restrict__ d) {
-    Template r;
-    const uint2 *p = reinterpret_cast<const uint2 *>(d->hdr);
-#pragma unroll
-    for (int q = 0; q < 7; ++q) {
-        const uint2 v = p[q];
-        r.t[2 * q] = v.x;
-        r.t[2 * q + 1] = v.y;
-    }
-    return r;
-}
+using Template = HeaderWords<14>;
 
 // What changes per segment (tcp/IpTcpProto_output.h:1069-1102, ip/IpStack.h:640-653).
 struct SegWords {
@@ -94,57 +68,26 @@ __device__ __forceinline__ SegWords ts_segment(const aipstack_tcp_burst *__restr
     return w;
 }
 
-// Little-endian halves of the source and destination address (frame bytes 26-33).
-__device__ __forceinline__ uint32_t ts_addr_halves(const Template &h) {
-    return (h.t[6] >> 16) + (h.t[7] & 0xFFFFu) + (h.t[7] >> 16) + (h.t[8] & 0xFFFFu);
-}
-
-// The IPv4 header checksum: version/IHL/DSCP, flags/fragment offset, TTL/protocol and the
-// addresses from the template, total length and ident per segment, the field as 0.
+// The IPv4 header checksum: what ip_header_checksum takes from the template, its flags/fragment
+// offset word, and total length and ident per segment.
 __device__ __forceinline__ uint32_t ts_ip_checksum(const Template &h, const SegWords &w) {
-    const uint32_t le = (h.t[3] >> 16) + (h.t[5] & 0xFFFFu) + (h.t[5] >> 16) + ts_addr_halves(h);
-    const uint32_t be = bswap16(fold16(le)) + w.total_len + w.ident;
-    return ~fold16(be) & 0xFFFFu;
+    return ip_header_checksum(h, h.t[5] & 0xFFFFu, w.total_len + w.ident);
 }
 
 // The State the data chain is resumed from: the pseudo-header (addresses, protocol 6, tcp_len)
 // and the 20 TCP header bytes (ports, ack, window, urgent pointer from the template; seq and
 // offset/flags per segment; the checksum field as 0). At most 13 words: far below 2^32.
 __device__ __forceinline__ uint32_t ts_l4_seed(const Template &h, const SegWords &w) {
-    const uint32_t le = ts_addr_halves(h) + (h.t[8] >> 16) + (h.t[9] & 0xFFFFu) + (h.t[10] >> 16) +
+    const uint32_t le = addr_halves(h) + (h.t[8] >> 16) + (h.t[9] & 0xFFFFu) + (h.t[10] >> 16) +
                         (h.t[11] & 0xFFFFu) + (h.t[12] & 0xFFFFu) + (h.t[13] & 0xFFFFu);
     return bswap16(fold16(le)) + 6u + (20u + w.len) + (w.seq >> 16) + (w.seq & 0xFFFFu) +
            w.offset_flags;
 }
 
-// A burst's view of the caller's index: segments [sb, se), chunks [cb, ce).
-struct BurstRange {
-    uint64_t sb, se, cb, ce;
-};
-
-__device__ __forceinline__ BurstRange ts_range(const uint64_t *__restrict__ seg_index,
-                                               const uint64_t *__restrict__ chunk_base, uint64_t b) {
-    return BurstRange{seg_index[b], seg_index[b + 1], chunk_base[b], chunk_base[b + 1]};
-}
-
-__device__ __forceinline__ bool ts_burst_ok(const TcpBurstShape &s, const BurstRange &r,
-                                            uint64_t n_segments, uint64_t n_chunks) {
-    return s.valid && r.se >= r.sb && r.se - r.sb == s.S && r.se <= n_segments && r.ce >= r.cb &&
-           r.ce - r.cb == s.C && r.ce <= n_chunks;
-}
-
-// The chunk entries an invalid burst's index gives it, clipped to the table: [c0, c0 + cnt).
-__device__ __forceinline__ void ts_clip_chunks(const BurstRange &r, uint64_t n_chunks, uint64_t &c0,
-                                               uint64_t &cnt) {
-    c0 = r.cb < n_chunks ? r.cb : n_chunks;
-    cnt = r.ce >= r.cb ? r.ce - r.cb : 0u;
-    if (cnt > n_chunks - c0) cnt = n_chunks - c0;
-}
-
 __device__ __forceinline__ void ts_put_chunk(uint64_t *__restrict__ chunk_addr,
                                              uint32_t *__restrict__ chunk_len, uint64_t c,
                                              uint64_t n_chunks, uint64_t addr, uint32_t len) {
-    if (c < n_chunks) {  // (implied by ts_burst_ok; the table is never left whatever happens)
+    if (c < n_chunks) {  // (implied by owner_ok; the table is never left whatever happens)
         __builtin_nontemporal_store(addr, &chunk_addr[c]);
         __builtin_nontemporal_store(len, &chunk_len[c]);
     }
@@ -152,17 +95,17 @@ __device__ __forceinline__ void ts_put_chunk(uint64_t *__restrict__ chunk_addr,
 
 // Plan pass: segment i of the batch, owned by burst `b` (lane-varying or wave-uniform).
 __device__ __forceinline__ void ts_plan_segment(
-    const aipstack_tcp_burst *__restrict__ d, const BurstRange &r, uint64_t b, uint64_t i,
+    const aipstack_tcp_burst *__restrict__ d, const OwnerRange &r, uint64_t b, uint64_t i,
     uint64_t n_segments, uint64_t n_chunks, uint64_t *__restrict__ chunk_addr,
     uint32_t *__restrict__ chunk_len, uint64_t *__restrict__ chunk_index,
     uint32_t *__restrict__ seeds, uint64_t *__restrict__ records) {
     const TcpBurstShape s = tcp_burst_shape(*d);
-    const uint64_t k = i - r.sb;
+    const uint64_t k = i - r.eb;
     uint32_t seed = 0;
-    uint64_t rec = b & kRecBurstMask, ci;
-    if (ts_burst_ok(s, r, n_segments, n_chunks)) {
+    uint64_t rec = make_record(b, 0, false), ci;
+    if (owner_ok(s.valid, s.S, s.C, r, n_segments, n_chunks)) {
         const SegWords w = ts_segment(d, s, k);
-        const Template h = ts_template(d);
+        const Template h = load_header_words<14>(d->hdr);
         ci = r.cb + k + (k > s.straddle ? 1u : 0u);
         const uint64_t len0 = d->data_len[0];
         if (w.len != 0u) {
@@ -179,12 +122,12 @@ __device__ __forceinline__ void ts_plan_segment(
             }
         }
         seed = ts_l4_seed(h, w);
-        rec |= (uint64_t)ts_ip_checksum(h, w) << 40 | kRecValid;
+        rec = make_record(b, ts_ip_checksum(h, w), true);
     } else {
         // its chunk entries are emptied by the burst loop below; the segments share them out
         // in order so that the index stays non-decreasing
         uint64_t c0, cnt;
-        ts_clip_chunks(r, n_chunks, c0, cnt);
+        clip_chunks(r, n_chunks, c0, cnt);
         ci = c0 + (k < cnt ? k : cnt);
     }
     __builtin_nontemporal_store(ci, &chunk_index[i]);
@@ -201,52 +144,30 @@ __global__ __launch_bounds__(kBlock) void tcpseg_plan_kernel(
     const WaveStride ws;
     if (blockIdx.x == 0 && threadIdx.x == 0)
         __builtin_nontemporal_store(n_chunks, &chunk_index[n_segments]);
-    for (uint64_t base = uniform64(ws.first); base < n_segments; base += ws.step) {
-        // The wave's 64 segments mostly share one or two bursts: the owners of its first and
-        // last segment are found with wave-uniform searches, and each lane searches only
-        // between them (no step at all when they agree).
-        const uint64_t last = base + (kWave - 1) < n_segments ? base + (kWave - 1) : n_segments - 1;
-        const uint64_t j0 = uniform64(ts_upper_bound(seg_index, 0, n_bursts + 1, base));
-        const uint64_t j1 = uniform64(ts_upper_bound(seg_index, j0, n_bursts + 1, last));
-        const uint64_t i = base + ws.lane;
-        if (i >= n_segments) continue;
-        if (j0 == j1 && j0 >= 1 && j0 <= n_bursts) {
-            const uint64_t b = j0 - 1;  // uniform: descriptor and index loads are shared
-            const BurstRange r = ts_range(seg_index, chunk_base, b);
-            if (r.sb <= base && last < r.se) {
-                ts_plan_segment(bursts + b, r, b, i, n_segments, n_chunks, chunk_addr, chunk_len,
-                                chunk_index, seeds, records);
-                continue;
-            }
-        }
-        const uint64_t j = ts_upper_bound(seg_index, j0, j1, i);
-        bool owned = j >= 1 && j <= n_bursts;
-        BurstRange r{0, 0, 0, 0};
-        if (owned) {
-            r = ts_range(seg_index, chunk_base, j - 1);
-            owned = r.sb <= i && i < r.se;
-        }
-        if (owned) {
-            ts_plan_segment(bursts + (j - 1), r, j - 1, i, n_segments, n_chunks, chunk_addr,
-                            chunk_len, chunk_index, seeds, records);
-        } else {  // the index gives the segment to no burst (it does not run from 0 to n)
+    for_each_owned(
+        seg_index, n_bursts, n_segments, ws,
+        [&](uint64_t b, uint64_t i) {
+            ts_plan_segment(bursts + b, owner_range(seg_index, chunk_base, b), b, i, n_segments,
+                            n_chunks, chunk_addr, chunk_len, chunk_index, seeds, records);
+        },
+        [&](uint64_t j, uint64_t i) {
             __builtin_nontemporal_store(j == 0 ? (uint64_t)0 : n_chunks, &chunk_index[i]);
             __builtin_nontemporal_store(0u, &seeds[i]);
             __builtin_nontemporal_store((uint64_t)0, &records[i]);
-        }
-    }
+        });
     // Bursts that break the contract: their chunk entries are emptied (length 0 at address 0),
     // whether or not the index gives them a segment.
     for (uint64_t b = (uint64_t)blockIdx.x * kBlock + threadIdx.x; b < n_bursts; b += ws.step) {
-        const BurstRange r = ts_range(seg_index, chunk_base, b);
-        if (ts_burst_ok(tcp_burst_shape(bursts[b]), r, n_segments, n_chunks)) continue;
+        const OwnerRange r = owner_range(seg_index, chunk_base, b);
+        const TcpBurstShape s = tcp_burst_shape(bursts[b]);
+        if (owner_ok(s.valid, s.S, s.C, r, n_segments, n_chunks)) continue;
         uint64_t c0, cnt;
-        ts_clip_chunks(r, n_chunks, c0, cnt);
+        clip_chunks(r, n_chunks, c0, cnt);
         for (uint64_t c = c0; c < c0 + cnt; ++c) ts_put_chunk(chunk_addr, chunk_len, c, n_chunks, 0, 0);
     }
 }
 
-// Emit pass. LINES: hdr_stride == 64 and the ring starts on a 64-byte boundary.
+// Emit pass. LINES: ring_in_lines(hdr_base, hdr_stride).
 template <bool LINES>
 __global__ __launch_bounds__(kBlock) void tcpseg_emit_kernel(
     const aipstack_tcp_burst *__restrict__ bursts, const uint64_t *__restrict__ seg_index,
@@ -258,17 +179,17 @@ __global__ __launch_bounds__(kBlock) void tcpseg_emit_kernel(
         const uint64_t i = base + ws.lane;
         const bool active = i < n_segments;
         const uint64_t rec = active ? __builtin_nontemporal_load(&records[i]) : 0u;
-        const bool valid = (rec & kRecValid) != 0u;
+        const bool valid = record_valid(rec);
         uint32_t o[16];
 #pragma unroll
         for (int q = 0; q < 16; ++q) o[q] = 0u;
         if (valid) {
-            const uint64_t b = rec & kRecBurstMask;
+            const uint64_t b = record_owner(rec);
             const aipstack_tcp_burst *__restrict__ d = bursts + b;
             const TcpBurstShape s = tcp_burst_shape(*d);
             const SegWords w = ts_segment(d, s, i - seg_index[b]);
-            const Template h = ts_template(d);
-            const uint32_t ipchk = (uint32_t)(rec >> 40) & 0xFFFFu;
+            const Template h = load_header_words<14>(d->hdr);
+            const uint32_t ipchk = record_ip_checksum(rec);
             // the chain's sum (seed (+) data, not inverted); a TCP checksum of 0 stays 0
             const uint32_t l4chk = ~(uint32_t)__builtin_nontemporal_load(&sums[i]) & 0xFFFFu;
 #pragma unroll
@@ -283,21 +204,8 @@ __global__ __launch_bounds__(kBlock) void tcpseg_emit_kernel(
         }
         if (active)
             status[i] = (uint8_t)(valid ? AIPSTACK_RX_ACCEPT : AIPSTACK_TX_BURST_INVALID);
-        if constexpr (LINES) {
-            const uint64_t ok = __builtin_amdgcn_ballot_w64(valid);  // (valid: below n_segments)
-            store_wave_lines<4>(tile[ws.wave], ws.lane, hdr_base, base, ok, o);
-        } else if (valid) {
-            const uint64_t P = hdr_base + i * hdr_stride;
-#pragma unroll
-            for (int q = 0; q < 3; ++q)
-                *reinterpret_cast<global_t<u32x4, 1> *>(P + 16u * q) =
-                    u32x4{o[4 * q], o[4 * q + 1], o[4 * q + 2], o[4 * q + 3]};
-            *reinterpret_cast<global_t<uint32_t, 1> *>(P + 48u) = o[12];
-            *reinterpret_cast<global_t<uint16_t, 1> *>(P + 52u) = (uint16_t)o[13];
-            const uint32_t end = hdr_stride < 64u ? (uint32_t)hdr_stride : 64u;
-            for (uint32_t z = AIPSTACK_TCP_SEGMENT_HEADER; z < end; ++z)
-                *reinterpret_cast<global_t<uint8_t> *>(P + z) = 0u;
-        }
+        store_header_slot<LINES, AIPSTACK_TCP_SEGMENT_HEADER>(tile, ws, hdr_base, hdr_stride, base,
+                                                              valid, AIPSTACK_TCP_SEGMENT_HEADER, o);
     }
 }
 
@@ -335,11 +243,9 @@ extern "C" int aipstack_tcp_tx_segment(const aipstack_tcp_burst *d_bursts,
                                      flags & AIPSTACK_CHKSUM_JUST_WRITTEN, stream);
     if (st != AIPSTACK_CHKSUM_OK) return st;
     const uint64_t base = (uint64_t)(uintptr_t)d_hdr;
-    if (hdr_stride == 64u && (base & 63u) == 0u)
-        hipLaunchKernelGGL(tcpseg_emit_kernel<true>, dim3(blocks), dim3(kBlock), 0, s, d_bursts,
-                           d_seg_index, records, sums, base, hdr_stride, d_status, n);
-    else
-        hipLaunchKernelGGL(tcpseg_emit_kernel<false>, dim3(blocks), dim3(kBlock), 0, s, d_bursts,
-                           d_seg_index, records, sums, base, hdr_stride, d_status, n);
+    const auto emit = ring_in_lines(base, hdr_stride) ? tcpseg_emit_kernel<true>
+                                                      : tcpseg_emit_kernel<false>;
+    hipLaunchKernelGGL(emit, dim3(blocks), dim3(kBlock), 0, s, d_bursts, d_seg_index, records, sums,
+                       base, hdr_stride, d_status, n);
     return check_hip(hipGetLastError());
 }
