@@ -1,8 +1,9 @@
 // TEST INFRASTRUCTURE -- answers of the reference's own fragment-length rounding and checksum
 // code (proto/Ip4Proto.h Ip4RoundFragLen; infra/Chksum.h IpChksum and IpChksumAccumulator),
 // compiled against the reference tree by tests/golden/ip_frag_ref.py, which records them in
-// tests/golden/ip_frag_ref_cases.json. send_fragmented itself needs the whole stack and is not
-// called. Reads one request per line:
+// tests/golden/ip_frag_ref_cases.json. send_fragmented itself needs the whole stack: it is not
+// called here but by oracle/stack_ref_gen.cpp, which runs the reference's IpStack on a capture
+// driver (tests/golden/stack_tx_ref_cases.json). Reads one request per line:
 //   R <mtu>                                  -> Ip4RoundFragLen(20, mtu)
 //   H <40 hex digits: 20 header bytes>       -> IpChksum(header, 20)
 //   U <src> <dst> <sport> <dport> <hex payload, or ->   (hex fields)

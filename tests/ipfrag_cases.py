@@ -6,7 +6,9 @@ UdpApi::sendUdpIp4Packet (udp/IpUdpProto.h:152-184) + IpStack::sendIp4Dgram (ip/
 + send_fragmented (:467-539), written independently of the kernels: send_fragmented's loop as a
 loop (a remaining length that shrinks, not the closed form of the library), the checksums from the
 CPU oracle over the bytes (pseudo-header + UDP header + payload; each 20-byte IPv4 header).
-test_ipfrag_host.py pins it against code compiled from the reference.
+test_ipfrag_host.py pins its leaf functions (Ip4RoundFragLen, two checksums) against code compiled
+from the reference; test_stack_tx_ref_host.py holds the whole model to the packets the reference
+stack emits (tests/golden/stack_tx_ref_cases.json).
 
 A datagram case is a dict: ``pieces`` ((offset, length) x 2 into the batch's payload buffer),
 ``mtu``, ``ip_id``, ``reserved``, ``hdr`` (48 template bytes); for a datagram that breaks the

@@ -5,8 +5,9 @@ The model is a plain Python restatement of the reference's send loop for one bur
 pcb_output_segment (tcp/IpTcpProto_output.h:1069-1102) + PcbOutputHelper::sendSegment (:1236-1284)
 + IpStack::sendIp4DgramFast (ip/IpStack.h:632-663), written independently of the kernels: the
 per-segment fields by the reference's rules, the checksums from the CPU oracle over the bytes
-(pseudo-header + TCP header + data; the IPv4 header). test_tcpseg_host.py pins it against code
-compiled from the reference.
+(pseudo-header + TCP header + data; the IPv4 header). test_tcpseg_host.py pins its checksum call
+sequences against code compiled from the reference; test_stack_tx_ref_host.py holds the whole
+model to the segments the reference stack emits (tests/golden/stack_tx_ref_cases.json).
 
 A burst case is a dict: ``pieces`` ((offset, length) x 2 into the batch's payload buffer),
 ``seq``, ``psh_offset``, ``mss``, ``ip_id``, ``flags``, ``reserved`` (3 bytes), ``hdr`` (56
