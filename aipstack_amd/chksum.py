@@ -1357,6 +1357,158 @@ def tx_linearise(frames, offsets, segments=None, *, headers=None, hdr_stride=Non
                            frame_max, lens, status, just_written, stream)
 
 
+AIPSTACK_ICMP_RESPONSE_HEADER = 42   # Ethernet 14 + IPv4 20 + ICMP 8
+AIPSTACK_ICMP_NONE = 23              # icmp_rx_respond: no response for this frame
+AIPSTACK_ICMP_ECHO_REPLY = 24
+AIPSTACK_ICMP_UNREACH = 25
+AIPSTACK_ICMP_TOO_LARGE = 26         # a response is due but 28 + data > mtu: left to the host
+AIPSTACK_ICMP_NO_UNREACH = 0xFF      # unreach_code[i]: no request
+AIPSTACK_ICMP_ALLOW_BROADCAST_PING = 1
+
+# ``aipstack_icmp_iface`` (chksum.h): the receiving interface, host-made.
+ICMP_IFACE_DTYPE = np.dtype({
+    "names": ["local_addr", "bcast_addr", "mtu", "ip_id", "ttl", "flags", "mac", "reserved"],
+    "formats": ["<u4", "<u4", "<u2", "<u2", "u1", "u1", ("u1", (6,)), ("u1", (12,))],
+    "offsets": [0, 4, 8, 10, 12, 13, 14, 20],
+    "itemsize": 32,
+})
+assert ICMP_IFACE_DTYPE.itemsize == 32
+
+
+def icmp_iface(local_addr: int, bcast_addr: int, mac, *, mtu: int = 1500, ip_id: int = 0,
+               ttl: int = 64, allow_broadcast_ping: bool = False) -> np.ndarray:
+    """One ``ICMP_IFACE_DTYPE`` record (addresses in host byte order, ``mac``: 6 bytes)."""
+    f = np.zeros(1, dtype=ICMP_IFACE_DTYPE)
+    f["local_addr"], f["bcast_addr"], f["mtu"], f["ip_id"], f["ttl"] = (
+        local_addr, bcast_addr, mtu, ip_id & 0xFFFF, ttl)
+    f["flags"] = AIPSTACK_ICMP_ALLOW_BROADCAST_PING if allow_broadcast_ping else 0
+    f["mac"][0] = np.frombuffer(bytes(mac), dtype=np.uint8)
+    return f
+
+
+def icmp_rx_respond_workspace_bytes(n: int) -> int:
+    """``aipstack_icmp_rx_respond_workspace_bytes``: the workspace :func:`icmp_rx_respond` needs
+    for n frames."""
+    return int(_lib.load().aipstack_icmp_rx_respond_workspace_bytes(max(n, 0)))
+
+
+class IcmpResponses:
+    """What :func:`icmp_rx_respond` leaves (device tensors, n frames): ``headers`` (uint8, n slots
+    of ``hdr_stride`` bytes; slot i holds frame i's response), ``hdr_lens`` (int32: 42 or 0), the
+    compact chunk table ``chunk_addr`` (int64, n) / ``chunk_len`` (int32, n) / ``chunk_index``
+    (int64, n + 1), ``status`` (uint8: AIPSTACK_ICMP_*), ``verdict`` (uint8: Rx verify's),
+    ``response_frame`` (int64, n: the frame index of response j, -1 beyond the count) and
+    ``counts`` (int64, 2: responses, chunks). Headers, lengths and the chunk table are the
+    arguments of :func:`tx_fill_header_split`; the object is a ``segments`` argument of
+    :func:`tx_linearise` / :func:`tx_linearise_slotted` (a frame without a response is skipped)."""
+
+    def __init__(self, headers, hdr_stride, hdr_lens, chunk_addr, chunk_len, chunk_index, status,
+                 verdict, response_frame, counts):
+        self.headers, self.hdr_stride, self.hdr_lens = headers, hdr_stride, hdr_lens
+        self.chunk_addr, self.chunk_len, self.chunk_index = chunk_addr, chunk_len, chunk_index
+        self.status, self.verdict = status, verdict
+        self.response_frame, self.counts = response_frame, counts
+
+    @property
+    def n(self) -> int:
+        return self.chunk_index.numel() - 1
+
+
+_ICMP_OUTS = (("hdr_lens", 4, 0), ("chunk_addr", 8, 0), ("chunk_len", 4, 0), ("chunk_index", 8, 1),
+              ("status", 1, 0), ("verdict", 1, 0), ("response_frame", 8, 0))
+
+
+def _icmp_call(name, frames, where, n, iface, unreach_code, hdr_stride, headers, workspace, out,
+               stream):
+    """What the two responder entry points share: the outputs (fresh, or those of ``out``), the
+    workspace, the call `name` on n frames laid out by `where`."""
+    torch = _torch()
+    lib = _lib.load()
+    f = np.ascontiguousarray(iface, dtype=ICMP_IFACE_DTYPE).reshape(-1)
+    if f.size != 1:
+        raise ValueError("iface must be one ICMP_IFACE_DTYPE record")
+    dev = frames.device
+    if out is not None:
+        headers, hdr_stride = out.headers, out.hdr_stride
+    if headers is None:
+        headers = torch.zeros(max(n, 1) * hdr_stride, dtype=torch.uint8, device=dev)
+    _require_device(headers, "headers")
+    _same_device(frames, headers, "frames and headers")
+    if headers.element_size() != 1 or hdr_stride <= 0 or headers.numel() < n * hdr_stride:
+        raise ValueError("headers must be a uint8 device tensor of n whole slots of hdr_stride bytes")
+    if out is None:
+        dt = {1: torch.uint8, 4: torch.int32, 8: torch.int64}
+        outs = {k: torch.empty(n + extra, dtype=dt[size], device=dev) for k, size, extra in _ICMP_OUTS}
+        outs["counts"] = torch.empty(2, dtype=torch.int64, device=dev)
+    else:
+        outs = {k: getattr(out, k) for k, _, _ in _ICMP_OUTS}
+        outs["counts"] = out.counts
+        for k, size, count in [(k, size, n + extra) for k, size, extra in _ICMP_OUTS] + [("counts", 8, 2)]:
+            t = outs[k]
+            _require_device(t, f"out.{k}")
+            _same_device(frames, t, f"frames and out.{k}")
+            if t.element_size() != size or t.numel() != count:
+                raise ValueError(f"out.{k} must hold {count} {size}-byte elements")
+    if unreach_code is not None:
+        _require_device(unreach_code, "unreach_code")
+        _same_device(frames, unreach_code, "frames and unreach_code")
+        if unreach_code.element_size() != 1 or unreach_code.numel() < n:
+            raise ValueError("unreach_code must be a uint8 device tensor with >= n elements")
+    res = IcmpResponses(headers, hdr_stride, outs["hdr_lens"], outs["chunk_addr"], outs["chunk_len"],
+                        outs["chunk_index"], outs["status"], outs["verdict"], outs["response_frame"],
+                        outs["counts"])
+    if n == 0:  # nothing to launch: the index's one entry and the counts are 0, every other output is empty
+        res.chunk_index.zero_()
+        res.counts.zero_()
+        return res
+    workspace, ws_bytes = _workspace(workspace, icmp_rx_respond_workspace_bytes(n), frames, "frames")
+    launch_stream = _launch_stream(stream, dev)
+    _check(getattr(lib, name)(
+        frames.data_ptr(), *where, n, f.ctypes.data,
+        unreach_code.data_ptr() if unreach_code is not None else None, res.verdict.data_ptr(),
+        res.status.data_ptr(), headers.data_ptr(), hdr_stride, res.hdr_lens.data_ptr(),
+        res.chunk_addr.data_ptr(), res.chunk_len.data_ptr(), res.chunk_index.data_ptr(),
+        res.response_frame.data_ptr(), res.counts.data_ptr(), workspace.data_ptr(), ws_bytes,
+        _stream_handle(launch_stream)), name)
+    workspace.record_stream(launch_stream)
+    return res
+
+
+def icmp_rx_respond(frames, offsets, iface, unreach_code=None, *, hdr_stride: int = 64,
+                    headers=None, workspace=None, out=None, stream=None) -> IcmpResponses:
+    """Rx verify plus the ICMP responder on the GPU (``aipstack_icmp_rx_respond``): frame i =
+    ``frames[offsets[i]:offsets[i+1]]``. For every echo request the reference would answer, and for
+    every frame the host asks a Destination Unreachable for (``unreach_code``: a uint8 device
+    tensor, the ICMP code per frame or ``AIPSTACK_ICMP_NO_UNREACH``; ``None`` = no requests) and
+    the reference would send one, the response's 42 header bytes go to slot i of the header ring
+    and its data becomes one chunk that points into ``frames``: nothing is copied. ``iface``: an
+    ``ICMP_IFACE_DTYPE`` record (:func:`icmp_iface`); response j in frame order carries the Ident
+    ``ip_id + j``. ``headers``: the ring to write (device uint8 tensor of at least n slots of
+    ``hdr_stride`` bytes; else a fresh, zeroed one); ``out``: an :class:`IcmpResponses` whose
+    tensors are reused; ``workspace``: a device tensor of at least
+    :func:`icmp_rx_respond_workspace_bytes` bytes, 8-byte aligned. Returns an
+    :class:`IcmpResponses` (chksum.h has the rules and the byte layout). With no frame at all
+    nothing runs: ``chunk_index`` (one entry) and ``counts`` are set to 0 and the header ring is
+    left as it is."""
+    _require_device(frames, "frames")
+    _require_offsets(offsets)
+    _same_device(frames, offsets, "frames and offsets")
+    n = max(offsets.numel() - 1, 0)
+    return _icmp_call("aipstack_icmp_rx_respond", frames, (offsets.data_ptr(),), n, iface,
+                      unreach_code, hdr_stride, headers, workspace, out, stream)
+
+
+def icmp_rx_respond_slotted(frames, slot_stride: int, lens, iface, unreach_code=None, *,
+                            hdr_stride: int = 64, headers=None, workspace=None, out=None,
+                            stream=None) -> IcmpResponses:
+    """:func:`icmp_rx_respond` on a ring of frame slots (frame i = the lens[i] bytes at
+    ``frames[i*slot_stride:]``, as :func:`rx_verify_slotted`)."""
+    _require_device(frames, "frames")
+    n = _require_lens(lens, frames.numel() * frames.element_size(), slot_stride, frames)
+    return _icmp_call("aipstack_icmp_rx_respond_slotted", frames, (slot_stride, lens.data_ptr()),
+                      n, iface, unreach_code, hdr_stride, headers, workspace, out, stream)
+
+
 class SplitFrames:
     """What :func:`split_frames` returns (host arrays): ``headers`` (n slots of ``hdr_stride``
     bytes), ``hdr_lens`` (uint32), ``payload`` (uint8, every chunk's bytes) and ``chunks``

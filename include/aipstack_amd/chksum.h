@@ -440,7 +440,7 @@ int aipstack_tcp_tx_segment(const aipstack_tcp_burst *d_bursts, const uint64_t *
  * fits its MTU), the chunk table of its data, the IPv4 header checksums and the UDP checksum, in
  * the layout aipstack_chksum_tx_fill_hsplit, aipstack_chksum_batch_chain and a scatter-gather
  * sender take. Routing, the source-address check (checkSendIp4Allowed), ARP and the decision to
- * send stay with the host; ICMP sends and IPv4 options are not covered. */
+ * send stay with the host; IPv4 options are not covered (ICMP sends: aipstack_icmp_rx_respond). */
 #define AIPSTACK_UDP_FIRST_FRAGMENT_HEADER 42u /* Ethernet 14 + IPv4 20 (IHL 5) + UDP 8 */
 #define AIPSTACK_UDP_NEXT_FRAGMENT_HEADER  34u /* Ethernet 14 + IPv4 20: fragments after the first */
 #define AIPSTACK_UDP_MIN_MTU 256u              /* the reference's MinMTU (ip/IpStack.h:255) */
@@ -698,6 +698,128 @@ int aipstack_ip4_rx_reassemble_slotted(const void *d_base, uint64_t slot_stride,
                                        uint32_t *d_chunk_len, uint32_t *d_next, uint32_t *d_head,
                                        aipstack_ip4_dgram *d_dgram, void *d_workspace,
                                        uint64_t workspace_bytes, void *stream);
+
+/* ---- ICMP on receive: echo replies and Destination Unreachable as Tx segments ------------ */
+
+/* Every ICMP message the reference sends goes through IpStack::sendIcmp4Message
+ * (ip/IpStack.h:1164-1190), from two callers: the echo reply (recvIcmp4Dgram ->
+ * sendIcmp4EchoReply, :1093-1162; its data is the request's ICMP data, chained in place) and
+ * Destination Unreachable (sendIp4DestUnreach, :869-887, which udp/IpUdpProto.h:609-620 calls for
+ * a datagram nobody accepted; its data is the received IPv4 header plus at most 8 bytes behind
+ * it). In both the data is one contiguous range of the received frame, so a response is a header
+ * slot plus one chunk that points into the Rx buffer: the layout aipstack_chksum_tx_fill_hsplit,
+ * aipstack_chksum_batch_chain and aipstack_tx_linearise take. These calls decide per frame whether
+ * a response is due and emit it; frames in, response segments out, nothing copied.
+ * Stays with the host: whether an unreach should be sent at all (the listener match, `accepted`,
+ * the code: it says so per frame in d_unreach_code), the next hop (the reference resolves it by
+ * ARP, eth/EthIpIface.h; the response's Ethernet destination is the received frame's source MAC
+ * and the host may overwrite those six bytes), a response above the MTU (the reference fragments
+ * it: AIPSTACK_ICMP_TOO_LARGE), and datagrams that aipstack_ip4_rx_reassemble completes: a
+ * fragment (verdict 3) never gets a response here. */
+#define AIPSTACK_ICMP_RESPONSE_HEADER 42u /* Ethernet 14 + IPv4 20 (IHL 5) + ICMP 8 */
+#define AIPSTACK_ICMP_NONE        23  /* per frame: no response */
+#define AIPSTACK_ICMP_ECHO_REPLY  24
+#define AIPSTACK_ICMP_UNREACH     25
+#define AIPSTACK_ICMP_TOO_LARGE   26  /* a response is due but 28 + data > mtu: the reference fragments
+                                         (sendIp4Dgram, no DF); left to the host, nothing emitted, no Ident used */
+#define AIPSTACK_ICMP_NO_UNREACH  0xFF /* d_unreach_code[i]: no request */
+#define AIPSTACK_ICMP_ALLOW_BROADCAST_PING 1u /* iface flag: IpStackOptions::AllowBroadcastPing */
+
+typedef struct aipstack_icmp_iface {  /* 32 bytes, host-made, host byte order; HOST memory */
+    uint32_t local_addr;   /* m_addr.addr (the interface has an address: m_have_addr) */
+    uint32_t bcast_addr;   /* m_addr.bcastaddr */
+    uint16_t mtu;          /* IP MTU, >= AIPSTACK_UDP_MIN_MTU */
+    uint16_t ip_id;        /* Ident of the first response; response j gets ip_id + j mod 2^16
+                              (m_next_id++ once per sent message, ip/IpStack.h:434) */
+    uint8_t  ttl;          /* IpStackOptions::IcmpTTL (default 64) */
+    uint8_t  flags;        /* AIPSTACK_ICMP_ALLOW_BROADCAST_PING */
+    uint8_t  mac[6];       /* Ethernet source of the responses */
+    uint8_t  reserved[12]; /* 0 */
+} aipstack_icmp_iface;
+
+/* The batch (frames as aipstack_chksum_rx_verify / _rx_verify_slotted take them, under the same
+ * offsets, span and slot contracts). h_iface: HOST memory, read before the call returns.
+ * d_unreach_code: NULL (no requests) or n bytes: the ICMP code of a Destination Unreachable the
+ * host wants for frame i, AIPSTACK_ICMP_NO_UNREACH for none.
+ *
+ * Which frames get a response (src / dst = the received IPv4 addresses):
+ *   echo reply  Rx verify accepts the frame (AIPSTACK_RX_ACCEPT: ICMP >= 8 bytes, checksum good,
+ *               :1116, :1127), protocol 1, ICMP type 8 (the code is not looked at, :1137); src
+ *               is not all-ones, not multicast ((src & 0xF0000000) == 0xE0000000) and not
+ *               bcast_addr (checkUnicastSrcAddr, :838-843); dst is local_addr, or bcast_addr or
+ *               all-ones with AIPSTACK_ICMP_ALLOW_BROADCAST_PING (:1103-1113, :1140).
+ *   unreach     no echo reply is due; d_unreach_code[i] != 0xFF; verdict AIPSTACK_RX_ACCEPT,
+ *               _ACCEPT_NO_CHKSUM or _ACCEPT_OTHER; dst == local_addr and src neither all-ones
+ *               nor bcast_addr (checkSendIp4Allowed with {dst, src}, :666-690; a multicast source
+ *               is not rejected there, nor here).
+ * A response with 28 + data > mtu is AIPSTACK_ICMP_TOO_LARGE: nothing is emitted for it and it
+ * takes no Ident here (the reference's fragmented send consumes one: the host that takes this
+ * slow path advances ip_id itself).
+ *
+ * The response bytes, for the j-th response in frame order:
+ *   Ethernet  destination = the frame's source MAC, source = mac, EtherType 0x0800;
+ *   IPv4      (sendIp4Dgram, :423-453) 0x4500 (IHL 5 whatever options the request carried), total
+ *             length 28 + data, Ident ip_id + j, flags / offset 0, TTL ttl, protocol 1, source =
+ *             local_addr (echo) or dst (unreach: the same value), destination = src, the header
+ *             checksum;
+ *   ICMP      (:1171-1185) echo reply: type 0, code 0, the request's `rest` (header bytes 4-7),
+ *             data = the request's ICMP data, IP-payload bytes [8, total length - 4*IHL)
+ *             (Ethernet padding is not data); unreach: type 3, the host's code, rest 0, data = the
+ *             received IPv4 header with its options plus the first min(8, total length - 4*IHL)
+ *             bytes behind it (:878-883). Checksum = IpChksum over the 8 header bytes with the
+ *             field as 0, then the data, stored as computed (a computed 0 stays 0x0000). The echo
+ *             checksum follows from the verified request's field by one's-complement arithmetic
+ *             except where rest + data sum to 0 mod 0xFFFF: there the reference stores 0xFFFF if
+ *             all those bytes are zero and 0x0000 otherwise, and the data is read to decide.
+ *
+ * Outputs, all written for all n frames in every call (outputs depend on inputs only):
+ *   d_verdict[i]   Rx verify's verdict, unchanged;
+ *   d_status[i]    AIPSTACK_ICMP_NONE / _ECHO_REPLY / _UNREACH / _TOO_LARGE;
+ *   d_hdr_len[i]   42 for a response, else 0 (aipstack_tx_linearise skips such a segment);
+ *   header slots   a response's 42 bytes at d_hdr + i*hdr_stride (hdr_stride >= 42), the slot's
+ *                  bytes [42, min(hdr_stride, 64)) written as 0 (a 64-byte ring on a 64-byte
+ *                  boundary is stored in whole lines), bytes past 64 untouched; the slot of a
+ *                  frame without a response is untouched;
+ *   chunk table    compact, in the form and contract of aipstack_chksum_batch_chain: no empty
+ *                  chunks; d_chunk_index has n+1 entries with steps of 0 or 1; a response with
+ *                  data has one chunk, the DEVICE address of the data where it lies in the Rx
+ *                  buffer and its length (an echo reply without data has none). d_chunk_addr /
+ *                  d_chunk_len hold n entries each; those at and beyond d_chunk_index[n] are
+ *                  written as address 0, length 0;
+ *   d_response_frame  n entries: entry j = the frame index of the j-th response, entries at and
+ *                  beyond the count written as ~0;
+ *   d_counts[2]    [0] the number of responses, [1] the number of chunks.
+ *
+ * Stream-ordered launches through the caller's workspace (8-byte aligned, at least
+ * aipstack_icmp_rx_respond_workspace_bytes(n) = 16 * (ceil(n / 256) + 1) bytes, free again once
+ * the stream passes the call): Rx verify, unchanged; a decide pass (one frame per lane: of an
+ * accepted frame at most the first 82 header bytes, never past the frame's own length; d_status;
+ * per 256-frame block the number of responses and chunks); a scan of the block counts by one
+ * workgroup; an emit pass (each responder's slot, table entry and list entry at its place in
+ * frame order; the tails of the lists). No kernel waits for another workgroup. Never allocates or
+ * synchronises; can be captured into a graph and repeated. _EINVAL before any work for a null
+ * pointer other than d_unreach_code, hdr_stride < 42, mtu < 256, a flag bit other than
+ * _ALLOW_BROADCAST_PING, a reserved byte that is not 0, n > 2^40, d_chunk_addr / d_chunk_index /
+ * d_response_frame / d_counts or the workspace not 8-byte aligned, d_hdr_len / d_chunk_len not
+ * 4-byte aligned, a short workspace, a slot stride outside (0, AIPSTACK_CHKSUM_MAX_SLOT_STRIDE];
+ * n == 0 is a no-op. */
+uint64_t aipstack_icmp_rx_respond_workspace_bytes(uint64_t n);
+int aipstack_icmp_rx_respond(const void *d_base, const uint64_t *d_offsets, uint64_t n,
+                             const aipstack_icmp_iface *h_iface, const uint8_t *d_unreach_code,
+                             uint8_t *d_verdict, uint8_t *d_status, void *d_hdr,
+                             uint64_t hdr_stride, uint32_t *d_hdr_len, uint64_t *d_chunk_addr,
+                             uint32_t *d_chunk_len, uint64_t *d_chunk_index,
+                             uint64_t *d_response_frame, uint64_t *d_counts, void *d_workspace,
+                             uint64_t workspace_bytes, void *stream);
+int aipstack_icmp_rx_respond_slotted(const void *d_base, uint64_t slot_stride,
+                                     const uint32_t *d_len, uint64_t n,
+                                     const aipstack_icmp_iface *h_iface,
+                                     const uint8_t *d_unreach_code, uint8_t *d_verdict,
+                                     uint8_t *d_status, void *d_hdr, uint64_t hdr_stride,
+                                     uint32_t *d_hdr_len, uint64_t *d_chunk_addr,
+                                     uint32_t *d_chunk_len, uint64_t *d_chunk_index,
+                                     uint64_t *d_response_frame, uint64_t *d_counts,
+                                     void *d_workspace, uint64_t workspace_bytes, void *stream);
 
 /* ---- 3. host-memory streaming engine ----------------------------------------------- */
 
