@@ -1509,6 +1509,154 @@ def icmp_rx_respond_slotted(frames, slot_stride: int, lens, iface, unreach_code=
                       n, iface, unreach_code, hdr_stride, headers, workspace, out, stream)
 
 
+AIPSTACK_UDP_NO_ASSOC = 0xFFFFFFFF
+AIPSTACK_UDP_ASSOC_NONLOCAL = 0x80000000   # association cookie bit 31: accept_nonlocal_dst
+AIPSTACK_UDP_MAX_LISTENERS = 64
+AIPSTACK_UDP_LIS_BROADCAST = 1             # UdpListenParams::accept_broadcast
+AIPSTACK_UDP_LIS_NONLOCAL = 2              # UdpListenParams::accept_nonlocal_dst
+AIPSTACK_UDP_DGRAM_VALID = 0x80
+AIPSTACK_UDP_DGRAM_HAS_CHKSUM = 1          # UdpRxInfo::has_checksum
+AIPSTACK_UDP_DGRAM_DST_LOCAL = 2           # the destination is the interface's address
+AIPSTACK_UDP_DGRAM_DST_BCAST = 4           # all-ones or the subnet broadcast
+
+# ``aipstack_udp_listener`` (chksum.h): one entry of the listener table, in list order.
+UDP_LISTENER_DTYPE = np.dtype({
+    "names": ["iface_addr", "port", "flags", "reserved0", "cookie", "reserved1"],
+    "formats": ["<u4", "<u2", "u1", "u1", "<u4", "<u4"],
+    "offsets": [0, 4, 6, 7, 8, 12],
+    "itemsize": 16,
+})
+# ``aipstack_udp_rx_dgram`` (chksum.h): one demultiplexed UDP datagram, host byte order.
+UDP_RX_DGRAM_DTYPE = np.dtype({
+    "names": ["remote_addr", "local_addr", "remote_port", "local_port", "data_off", "data_len",
+              "listeners", "assoc", "flags", "ttl", "reserved"],
+    "formats": ["<u4", "<u4", "<u2", "<u2", "<u2", "<u2", "<u8", "<u4", "u1", "u1", "<u2"],
+    "offsets": [0, 4, 8, 10, 12, 14, 16, 24, 28, 29, 30],
+    "itemsize": 32,
+})
+assert UDP_LISTENER_DTYPE.itemsize == 16 and UDP_RX_DGRAM_DTYPE.itemsize == 32
+
+
+def udp_rx_demux_workspace_bytes(n: int) -> int:
+    """``aipstack_udp_rx_demux_workspace_bytes``: the workspace :func:`udp_rx_demux` needs for n
+    frames."""
+    return int(_lib.load().aipstack_udp_rx_demux_workspace_bytes(max(n, 0)))
+
+
+class UdpRxDemuxed:
+    """What :func:`udp_rx_demux` leaves (device tensors, n frames): ``verdict`` (uint8: Rx
+    verify's), ``dgrams`` (uint8, n * 32 bytes: n ``aipstack_udp_rx_dgram`` records),
+    ``unreach_code`` (uint8: 3 or ``AIPSTACK_ICMP_NO_UNREACH``; the ``unreach_code`` argument of
+    :func:`icmp_rx_respond` as it is), ``deliver_frame`` (int64, n: the frame index of delivery
+    j, -1 beyond the count) and ``counts`` (int64, 2: deliveries, unreach requests)."""
+
+    def __init__(self, verdict, dgrams, unreach_code, deliver_frame, counts):
+        self.verdict, self.dgrams, self.unreach_code = verdict, dgrams, unreach_code
+        self.deliver_frame, self.counts = deliver_frame, counts
+
+    @property
+    def n(self) -> int:
+        return self.verdict.numel()
+
+    def dgrams_numpy(self) -> np.ndarray:
+        """The records on the host as a ``UDP_RX_DGRAM_DTYPE`` array (synchronises)."""
+        return self.dgrams[:self.n * 32].cpu().numpy().view(UDP_RX_DGRAM_DTYPE)
+
+
+def _udp_table(table, dtype, name, frames):
+    """(pointer, entries, tensor to keep alive) of a 16-byte-entry table: None, a device uint8
+    tensor of whole entries, or a host array of `dtype` (uploaded here)."""
+    torch = _torch()
+    if table is None:
+        return 0, 0, None
+    if not hasattr(table, "data_ptr"):
+        k = np.ascontiguousarray(table, dtype=dtype).reshape(-1)
+        if k.size == 0:
+            return 0, 0, None
+        table = torch.from_numpy(k.view(np.uint8).copy()).to(frames.device)
+    _require_device(table, name)
+    _same_device(table, frames, f"{name} and frames")
+    nbytes = table.numel() * table.element_size()
+    if nbytes % 16:
+        raise ValueError(f"{name} must hold whole 16-byte entries")
+    return (table.data_ptr() if nbytes else 0), nbytes // 16, table
+
+
+def _udp_out(t, count, size, name, frames):
+    torch = _torch()
+    if t is None:
+        return torch.empty(count, dtype={1: torch.uint8, 8: torch.int64}[size], device=frames.device)
+    _require_device(t, name)
+    _same_device(t, frames, f"{name} and frames")
+    if t.element_size() != size or t.numel() < count:
+        raise ValueError(f"{name} must be a device tensor of at least {count} {size}-byte elements")
+    return t
+
+
+def _udp_demux_call(name, frames, where, n, iface, assocs, listeners, verdict, dgrams,
+                    unreach_code, deliver_frame, counts, workspace, stream):
+    """What the two demux entry points share: the outputs, the tables (uploaded on the launch
+    stream), the workspace, the call `name` on n frames laid out by `where`."""
+    f = np.ascontiguousarray(iface, dtype=ICMP_IFACE_DTYPE).reshape(-1)
+    if f.size != 1:
+        raise ValueError("iface must be one ICMP_IFACE_DTYPE record")
+    res = UdpRxDemuxed(_u8_out(verdict, n, frames), _udp_out(dgrams, n * 32, 1, "dgrams", frames),
+                       _udp_out(unreach_code, n, 1, "unreach_code", frames),
+                       _udp_out(deliver_frame, n, 8, "deliver_frame", frames),
+                       _udp_out(counts, 2, 8, "counts", frames))
+    launch_stream = _launch_stream(stream, frames.device)
+    with _torch().cuda.stream(launch_stream):  # an upload is ordered before the call
+        ap, an, akeep = _udp_table(assocs, TCP_PCB_KEY_DTYPE, "assocs", frames)
+        lp, ln, lkeep = _udp_table(listeners, UDP_LISTENER_DTYPE, "listeners", frames)
+        if n == 0:  # nothing to launch: the counts are 0, every other output is empty
+            res.counts.zero_()
+            return res
+    workspace, ws_bytes = _workspace(workspace, udp_rx_demux_workspace_bytes(n), frames, "frames")
+    _check(getattr(_lib.load(), name)(
+        frames.data_ptr(), *where, n, f.ctypes.data, ap, an, lp, ln, res.verdict.data_ptr(),
+        res.dgrams.data_ptr(), res.unreach_code.data_ptr(), res.deliver_frame.data_ptr(),
+        res.counts.data_ptr(), workspace.data_ptr(), ws_bytes, _stream_handle(launch_stream)), name)
+    workspace.record_stream(launch_stream)
+    for keep, given in ((akeep, assocs), (lkeep, listeners)):
+        if keep is not None and keep is not given:
+            keep.record_stream(launch_stream)
+    return res
+
+
+def udp_rx_demux(frames, offsets, iface, assocs=None, listeners=None, *, verdict=None, dgrams=None,
+                 unreach_code=None, deliver_frame=None, counts=None, workspace=None,
+                 stream=None) -> UdpRxDemuxed:
+    """Rx verify plus the UDP demux on the GPU (``aipstack_udp_rx_demux``): frame i =
+    ``frames[offsets[i]:offsets[i+1]]``, all received on the interface ``iface`` (an
+    ``ICMP_IFACE_DTYPE`` record, :func:`icmp_iface`). For every frame accepted as UDP the
+    ``aipstack_udp_rx_dgram`` record: ports, where the data lies (cut to the UDP length), the
+    eligible association of ``assocs`` (a table of ``TCP_PCB_KEY_DTYPE`` entries sorted by
+    :func:`tcp_pcb_table_sort`; cookie bit 31 = accept_nonlocal_dst) and the mask of the matching
+    ``listeners`` (at most 64 ``UDP_LISTENER_DTYPE`` entries, newest first as the reference walks
+    them). Each table: a host array (uploaded on the launch stream), a device uint8 tensor
+    already resident, or ``None``. ``unreach_code`` is 3 where the reference would send a port
+    unreachable with no handler called. Returns a :class:`UdpRxDemuxed` (chksum.h has the rules)."""
+    _require_device(frames, "frames")
+    _require_offsets(offsets)
+    _same_device(frames, offsets, "frames and offsets")
+    n = max(offsets.numel() - 1, 0)
+    return _udp_demux_call("aipstack_udp_rx_demux", frames, (offsets.data_ptr(),), n, iface, assocs,
+                           listeners, verdict, dgrams, unreach_code, deliver_frame, counts, workspace,
+                           stream)
+
+
+def udp_rx_demux_slotted(frames, slot_stride: int, lens, iface, assocs=None, listeners=None, *,
+                         verdict=None, dgrams=None, unreach_code=None, deliver_frame=None,
+                         counts=None, workspace=None, stream=None) -> UdpRxDemuxed:
+    """:func:`udp_rx_demux` on a ring of frame slots (frame i = the lens[i] bytes at
+    ``frames[i*slot_stride:]``, as :func:`rx_verify_slotted`)."""
+    _require_device(frames, "frames")
+    n = _require_lens(lens, frames.numel() * frames.element_size(), slot_stride, frames)
+    return _udp_demux_call("aipstack_udp_rx_demux_slotted", frames, (slot_stride, lens.data_ptr()),
+                           n, iface, assocs, listeners, verdict, dgrams, unreach_code,
+                           deliver_frame, counts, workspace, stream)
+
+
 class SplitFrames:
     """What :func:`split_frames` returns (host arrays): ``headers`` (n slots of ``hdr_stride``
     bytes), ``hdr_lens`` (uint32), ``payload`` (uint8, every chunk's bytes) and ``chunks``

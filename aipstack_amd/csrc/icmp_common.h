@@ -40,6 +40,16 @@ inline IcmpIface icmp_iface_of(const aipstack_icmp_iface &f) {
                      (uint32_t)f.mac[4] | (uint32_t)f.mac[5] << 8};
 }
 
+// What the calls that take an aipstack_icmp_iface accept of it (the ICMP responder, and the UDP
+// Rx demux, whose struct goes to the responder next).
+inline bool icmp_iface_valid(const aipstack_icmp_iface &f) {
+    if (f.mtu < AIPSTACK_UDP_MIN_MTU || (f.flags & ~AIPSTACK_ICMP_ALLOW_BROADCAST_PING) != 0)
+        return false;
+    for (uint8_t r : f.reserved)
+        if (r != 0) return false;
+    return true;
+}
+
 AIPSTACK_ICMP_HD uint32_t icmp_bswap32(uint32_t x) {
     return x >> 24 | (x >> 8 & 0xFF00u) | (x << 8 & 0xFF0000u) | x << 24;
 }

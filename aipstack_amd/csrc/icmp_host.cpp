@@ -34,11 +34,7 @@ int icmp_rx_respond_check_args(const IcmpRespondArgs &a) {
         if (!p) return AIPSTACK_CHKSUM_EINVAL;
     if (a.n > kIcmpMaxCount || a.hdr_stride < AIPSTACK_ICMP_RESPONSE_HEADER)
         return AIPSTACK_CHKSUM_EINVAL;
-    const aipstack_icmp_iface &f = *a.h_iface;
-    if (f.mtu < AIPSTACK_UDP_MIN_MTU || (f.flags & ~AIPSTACK_ICMP_ALLOW_BROADCAST_PING) != 0)
-        return AIPSTACK_CHKSUM_EINVAL;
-    for (uint8_t r : f.reserved)
-        if (r != 0) return AIPSTACK_CHKSUM_EINVAL;
+    if (!icmp_iface_valid(*a.h_iface)) return AIPSTACK_CHKSUM_EINVAL;
     for (const void *p : {a.d_chunk_addr, a.d_chunk_index, a.d_response_frame, a.d_counts, a.d_workspace})
         if (((uintptr_t)p & 7u) != 0) return AIPSTACK_CHKSUM_EINVAL;
     if (((uintptr_t)a.d_hdr_len & 3u) != 0 || ((uintptr_t)a.d_chunk_len & 3u) != 0)

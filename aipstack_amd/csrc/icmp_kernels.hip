@@ -6,8 +6,8 @@
 //      verdict, the host's unreach code and, only of an accepted frame, its header bytes, read as
 //      dwords at the frame's own byte alignment and only inside the frame; d_status; the tile's
 //      number of responses and of chunks into the workspace;
-//   3. icmp_scan_kernel, ONE workgroup: the exclusive running sums of the tiles' counts in
-//      place, the totals behind them and into d_counts;
+//   3. pair_scan_kernel (pair_scan.h), ONE workgroup: the exclusive running sums of the tiles'
+//      counts in place, the totals behind them and into d_counts;
 //   4. icmp_emit_kernel, tiles as in 2: a responder's place j in frame order = its tile's sum +
 //      its rank in the tile (ballots and four wave totals in LDS), so its Ident, its entry of
 //      the compact chunk table and of d_response_frame; its slot (through LDS in whole lines when
@@ -24,6 +24,7 @@
 #include "chksum_internal.h"
 #include "icmp_common.h"
 #include "lane_pass.h"
+#include "pair_scan.h"
 #include "rx_frames.h"
 #include "tx_producer.h"
 
@@ -77,57 +78,6 @@ __global__ __launch_bounds__(kBlock) void icmp_decide_kernel(
             ws[2 * tile + threadIdx.x] = s;
         }
         __syncthreads();
-    }
-}
-
-// The inclusive running sum of v over the block's threads (v <= 256 each: below 2^32).
-__device__ __forceinline__ uint32_t block_inclusive_sum(uint32_t v, uint32_t (&tot)[kWaves],
-                                                        uint32_t lane, uint32_t wave) {
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) {
-        const uint32_t u = __shfl_up(v, d, kWave);
-        if (lane >= (uint32_t)d) v += u;
-    }
-    if (lane == kWave - 1) tot[wave] = v;
-    __syncthreads();
-#pragma unroll
-    for (int w = 0; w < kWaves; ++w)
-        if ((uint32_t)w < wave) v += tot[w];
-    __syncthreads();
-    return v;
-}
-
-// One workgroup: ws[2t], ws[2t+1] become the sums of the tiles before t; the totals go to
-// ws[2 * tiles], ws[2 * tiles + 1] and to counts[0..1].
-__global__ __launch_bounds__(kBlock) void icmp_scan_kernel(uint64_t tiles, uint64_t *__restrict__ ws,
-                                                           uint64_t *__restrict__ counts) {
-    __shared__ uint32_t tot[2][kWaves];
-    const uint32_t lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-    uint64_t carry_r = 0, carry_c = 0;  // the same in every thread
-    for (uint64_t base = 0; base < tiles; base += kBlock) {
-        const uint64_t t = base + threadIdx.x;
-        const bool in = t < tiles;
-        // (a tile's count is at most kIcmpTile)
-        const uint32_t r = in ? (uint32_t)ws[2 * t] : 0u, c = in ? (uint32_t)ws[2 * t + 1] : 0u;
-        const uint32_t ri = block_inclusive_sum(r, tot[0], lane, wave);
-        const uint32_t ci = block_inclusive_sum(c, tot[1], lane, wave);
-        if (in) {
-            ws[2 * t] = carry_r + (ri - r);
-            ws[2 * t + 1] = carry_c + (ci - c);
-        }
-        // the last thread's inclusive sums, to every thread
-        if (threadIdx.x == kBlock - 1) {
-            tot[0][0] = ri;
-            tot[1][0] = ci;
-        }
-        __syncthreads();
-        carry_r += tot[0][0];
-        carry_c += tot[1][0];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        ws[2 * tiles] = counts[0] = carry_r;
-        ws[2 * tiles + 1] = counts[1] = carry_c;
     }
 }
 
@@ -218,7 +168,7 @@ int launch_respond(const Frames &fr, uint64_t n, const IcmpIface &f, const uint8
     const uint64_t hdr_base = (uint64_t)(uintptr_t)o.hdr;
     hipLaunchKernelGGL((icmp_decide_kernel<Frames>), dim3(blocks), dim3(kBlock), 0, s, fr, n, f,
                        d_unreach, o.verdict, o.status, o.ws);
-    hipLaunchKernelGGL(icmp_scan_kernel, dim3(1), dim3(kBlock), 0, s, tiles, o.ws, o.counts);
+    hipLaunchKernelGGL(pair_scan_kernel, dim3(1), dim3(kBlock), 0, s, tiles, o.ws, o.counts);
     if (ring_in_lines(hdr_base, o.hdr_stride))
         hipLaunchKernelGGL((icmp_emit_kernel<Frames, true>), dim3(blocks), dim3(kBlock), 0, s, fr, n,
                            f, d_unreach, o.verdict, o.status, hdr_base, o.hdr_stride, o.hdr_len,

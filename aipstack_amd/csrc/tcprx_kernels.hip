@@ -26,27 +26,14 @@
 namespace aipstack_amd {
 namespace {
 
-// The cookie of the entry equal to `key` in the table sorted by tcp_pcb_key_compare. Every
-// entry read has an index in [lo, hi) within [0, n_pcbs), whatever the table holds; the range
-// shrinks by at least one entry per step.
+// The cookie of the entry equal to `key` in the table sorted by tcp_pcb_key_compare
+// (pcb_table_find, pcb_lookup.h: every entry read lies inside [0, n_pcbs)).
 __device__ __forceinline__ uint32_t rxp_lookup(const aipstack_tcp_pcb_key *__restrict__ pcbs,
                                                uint64_t n_pcbs, const aipstack_tcp_pcb_key &key) {
-    uint64_t lo = 0, hi = n_pcbs;
-    while (lo < hi) {
-        const uint64_t mid = lo + ((hi - lo) >> 1);
-        const u32x4 e =
-            *reinterpret_cast<global_t<const u32x4, 8> *>((uint64_t)(uintptr_t)pcbs + mid * 16u);
-        aipstack_tcp_pcb_key k;
-        k.local_addr = e.x;
-        k.remote_addr = e.y;
-        k.local_port = (uint16_t)(e.z & 0xFFFFu);
-        k.remote_port = (uint16_t)(e.z >> 16);
-        const int c = tcp_pcb_key_compare(k, key);
-        if (c == 0) return e.w;
-        if (c < 0) lo = mid + 1;
-        else hi = mid;
-    }
-    return AIPSTACK_TCP_NO_PCB;
+    uint32_t cookie;
+    return pcb_table_find(PcbTableLoad{(uint64_t)(uintptr_t)pcbs}, n_pcbs, key, cookie)
+               ? cookie
+               : AIPSTACK_TCP_NO_PCB;
 }
 
 // LINES: d_segs is 16-byte aligned.

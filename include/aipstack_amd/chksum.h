@@ -710,8 +710,9 @@ int aipstack_ip4_rx_reassemble_slotted(const void *d_base, uint64_t slot_stride,
  * slot plus one chunk that points into the Rx buffer: the layout aipstack_chksum_tx_fill_hsplit,
  * aipstack_chksum_batch_chain and aipstack_tx_linearise take. These calls decide per frame whether
  * a response is due and emit it; frames in, response segments out, nothing copied.
- * Stays with the host: whether an unreach should be sent at all (the listener match, `accepted`,
- * the code: it says so per frame in d_unreach_code), the next hop (the reference resolves it by
+ * Stays with this call's caller: whether an unreach should be sent at all (the listener match,
+ * `accepted`, the code: d_unreach_code says so per frame; aipstack_udp_rx_demux below writes that
+ * array for UDP). Stays with the host: the next hop (the reference resolves it by
  * ARP, eth/EthIpIface.h; the response's Ethernet destination is the received frame's source MAC
  * and the host may overwrite those six bytes), a response above the MTU (the reference fragments
  * it: AIPSTACK_ICMP_TOO_LARGE), and datagrams that aipstack_ip4_rx_reassemble completes: a
@@ -820,6 +821,118 @@ int aipstack_icmp_rx_respond_slotted(const void *d_base, uint64_t slot_stride,
                                      uint32_t *d_chunk_len, uint64_t *d_chunk_index,
                                      uint64_t *d_response_frame, uint64_t *d_counts,
                                      void *d_workspace, uint64_t workspace_bytes, void *stream);
+
+/* ---- UDP Rx demux: associations, listeners and port unreachable of a batch of frames ------ */
+
+/* What the reference does with a UDP datagram between its length check and the calls of the
+ * handlers (IpUdpProto::recvIp4Dgram, udp/IpUdpProto.h:470-621): read the ports, truncate the
+ * datagram to the UDP length (:492), look up the association (:527-537), walk the listener list
+ * with incomingPacketMatches (:255-289) and decide to send a port unreachable (:611-619) -- for a
+ * batch of frames in device memory. (The section stands behind the ICMP one because it takes its
+ * aipstack_icmp_iface; it continues the TCP Rx parse, whose key table and sort it shares.) The
+ * host's UDP Rx loop becomes "for each entry of d_deliver_frame: call the handlers the record
+ * names", and d_unreach_code goes to aipstack_icmp_rx_respond as it is.
+ * Stays with the host: calling the handlers and what they return (AcceptStop ends the walk;
+ * a host whose handlers all return Reject sets the frame's unreach code itself); updateCachedInfo
+ * after a callback that changes the interface address (:503-506, :560, :606: a host that does
+ * that re-evaluates the rest of that frame itself); the IP-level interface listeners of
+ * ip/IpStack.h:1059-1067; more than 64 listeners; datagrams that aipstack_ip4_rx_reassemble
+ * completes (a fragment, verdict 3, gets no record here). */
+#define AIPSTACK_UDP_NO_ASSOC        0xFFFFFFFFu
+#define AIPSTACK_UDP_ASSOC_NONLOCAL  0x80000000u /* table cookie bit 31: UdpAssociationParams::accept_nonlocal_dst */
+#define AIPSTACK_UDP_MAX_LISTENERS   64u
+#define AIPSTACK_UDP_LIS_BROADCAST   1u          /* UdpListenParams::accept_broadcast */
+#define AIPSTACK_UDP_LIS_NONLOCAL    2u          /* UdpListenParams::accept_nonlocal_dst */
+#define AIPSTACK_UDP_DGRAM_VALID        0x80u
+#define AIPSTACK_UDP_DGRAM_HAS_CHKSUM   1u       /* UdpRxInfo::has_checksum (:637) */
+#define AIPSTACK_UDP_DGRAM_DST_LOCAL    2u       /* dst_is_iface_addr (:504) */
+#define AIPSTACK_UDP_DGRAM_DST_BCAST    4u       /* is_bcast (:270-272) */
+
+typedef struct aipstack_udp_listener {  /* 16 bytes; DEVICE table, in the order the reference iterates
+                                           m_listeners_list (startListening prepends: newest first) */
+    uint32_t iface_addr;                /* UdpListenParams::iface_addr, 0 = any */
+    uint16_t port;                      /* 0 = any */
+    uint8_t  flags;                     /* AIPSTACK_UDP_LIS_* */
+    uint8_t  reserved0;                 /* 0 */
+    uint32_t cookie;                    /* the caller's handle; not read by the device */
+    uint32_t reserved1;                 /* 0 */
+} aipstack_udp_listener;
+
+typedef struct aipstack_udp_rx_dgram {  /* 32 bytes, host byte order; all zero unless _VALID */
+    uint32_t remote_addr, local_addr;   /* IPv4 source, destination */
+    uint16_t remote_port, local_port;   /* UDP source, destination */
+    uint16_t data_off;                  /* 14 + 4*IHL + 8, from the frame start */
+    uint16_t data_len;                  /* UDP length - 8 (:492), not the IPv4 length, not the frame's */
+    uint64_t listeners;                 /* bit k: listener k matches (incomingPacketMatches) */
+    uint32_t assoc;                     /* cookie & 0x7FFFFFFF of the eligible association, else _NO_ASSOC */
+    uint8_t  flags;                     /* AIPSTACK_UDP_DGRAM_* */
+    uint8_t  ttl;                       /* IpRxInfoIp4::ttl */
+    uint16_t reserved;                  /* 0 */
+} aipstack_udp_rx_dgram;
+
+/* The batch (frames as aipstack_chksum_rx_verify / _rx_verify_slotted take them, under the same
+ * offsets, span and slot contracts) comes from one interface, h_iface (HOST memory, read before
+ * the call returns; validated as aipstack_icmp_rx_respond validates it, because the same struct
+ * goes there next; only local_addr and bcast_addr are used here).
+ * d_assocs: n_assocs aipstack_tcp_pcb_key entries in DEVICE memory, {local_addr, remote_addr,
+ * local_port, remote_port} = UdpAssociationKey, sorted by aipstack_tcp_pcb_table_sort
+ * (AssociationKeyCompare, :436-441, has the field order of TcpPcbKeyCompare), keys unique; the
+ * cookie's low 31 bits are the caller's handle, bit 31 is accept_nonlocal_dst (n_assocs == 0: no
+ * table, d_assocs may be NULL). An unsorted table gives unspecified assoc values (and with them
+ * unspecified unreach codes and deliveries of the frames concerned), never an access outside the
+ * table.
+ * d_listeners: n_listeners <= 64 entries in DEVICE memory: the listeners whose `iface` parameter
+ * is null or is this interface (:266), in list order, so that bit k of a record names entry k
+ * (n_listeners == 0: d_listeners may be NULL). An entry is read by its defined bits only: set
+ * reserved bytes or other flag bits change nothing; the device does not validate the tables.
+ * Per frame i (src / dst = the received IPv4 addresses):
+ *   - d_verdict[i]: Rx verify's verdict, unchanged;
+ *   - d_dgrams[i]: a VALID record for verdict AIPSTACK_RX_ACCEPT or _ACCEPT_NO_CHKSUM with
+ *     protocol 17 (Rx verify has applied the length checks of :473-489; they are applied again so
+ *     that every read lies inside the frame); 32 zero bytes for every other frame. In it:
+ *     dst_local = (dst == local_addr); is_bcast = (dst == 0xFFFFFFFF || dst == bcast_addr);
+ *     has_checksum = the checksum field is not 0;
+ *     assoc: the association is the entry equal to {dst, src, dst port, src port}; it is eligible
+ *     when found and (cookie bit 31 set or dst_local) (:535), else assoc is _NO_ASSOC;
+ *     listeners bit k (:262-288): (port == 0 or port == dst port) and not (is_bcast without
+ *     _LIS_BROADCAST) and not (neither _LIS_NONLOCAL nor is_bcast nor dst_local) and (iface_addr
+ *     == 0 or iface_addr == the interface's local_addr);
+ *   - d_unreach_code[i]: 3 (Icmp4Code::DestUnreachPortUnreach) for a valid record with dst_local,
+ *     no eligible association and no matching listener (:611-619 with no handler ever called),
+ *     AIPSTACK_ICMP_NO_UNREACH for every other frame; written for all n frames. The source checks
+ *     of checkSendIp4Allowed stay in aipstack_icmp_rx_respond.
+ *   - d_deliver_frame: n entries: the indices of the frames with an eligible association or a
+ *     matching listener, in frame order; the entries at and beyond the count written as ~0;
+ *   - d_counts[2]: [0] the number of deliveries, [1] the number of code-3 requests.
+ * Stream-ordered launches through the caller's workspace (8-byte aligned, at least
+ * aipstack_udp_rx_demux_workspace_bytes(n) = 16 * (ceil(n / 256) + 1) + 32 * ceil(n / 256) bytes,
+ * free again once the stream passes the call): Rx verify, unchanged; a demux pass (one frame per
+ * lane: the listener table once per workgroup; of a frame accepted as UDP at most the first 82
+ * header bytes, never past the frame's own length; the records, the codes; per 256-frame block
+ * the number of deliveries and of requests and the delivery bits); a scan of the block counts by
+ * one workgroup; an emit pass (d_deliver_frame and its tail). No kernel waits for another
+ * workgroup. Never allocates or synchronises; can be captured into a graph and repeated (outputs
+ * depend on inputs only; every output is written for all n frames). _EINVAL before any work for
+ * a null pointer (but d_assocs with n_assocs == 0, d_listeners with n_listeners == 0), n or
+ * n_assocs above 2^40, n_listeners > 64, an interface aipstack_icmp_rx_respond rejects, d_dgrams
+ * / d_deliver_frame / d_counts / a table / the workspace not 8-byte aligned, a short workspace,
+ * a slot stride outside (0, AIPSTACK_CHKSUM_MAX_SLOT_STRIDE]; n == 0 is a no-op. */
+uint64_t aipstack_udp_rx_demux_workspace_bytes(uint64_t n);
+int aipstack_udp_rx_demux(const void *d_base, const uint64_t *d_offsets, uint64_t n,
+                          const aipstack_icmp_iface *h_iface,
+                          const aipstack_tcp_pcb_key *d_assocs, uint64_t n_assocs,
+                          const aipstack_udp_listener *d_listeners, uint32_t n_listeners,
+                          uint8_t *d_verdict, aipstack_udp_rx_dgram *d_dgrams,
+                          uint8_t *d_unreach_code, uint64_t *d_deliver_frame, uint64_t *d_counts,
+                          void *d_workspace, uint64_t workspace_bytes, void *stream);
+int aipstack_udp_rx_demux_slotted(const void *d_base, uint64_t slot_stride, const uint32_t *d_len,
+                                  uint64_t n, const aipstack_icmp_iface *h_iface,
+                                  const aipstack_tcp_pcb_key *d_assocs, uint64_t n_assocs,
+                                  const aipstack_udp_listener *d_listeners, uint32_t n_listeners,
+                                  uint8_t *d_verdict, aipstack_udp_rx_dgram *d_dgrams,
+                                  uint8_t *d_unreach_code, uint64_t *d_deliver_frame,
+                                  uint64_t *d_counts, void *d_workspace, uint64_t workspace_bytes,
+                                  void *stream);
 
 /* ---- 3. host-memory streaming engine ----------------------------------------------- */
 
