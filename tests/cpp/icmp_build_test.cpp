@@ -7,7 +7,7 @@
 //
 // One case per line:
 //   <local> <bcast> <mtu> <ttl> <flags> <mac hex> <verdict> <code> <ident> <status> <data_off>
-//   <data_len> <frame hex> <42 header bytes hex, or ->
+//   <data_len> <frame hex, or - for an empty frame> <42 header bytes hex, or ->
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -47,6 +47,7 @@ struct HeapLoad {
 };
 
 static std::vector<uint8_t> unhex(const std::string &h) {
+    if (h == "-") return {};  // a frame of no bytes at all
     std::vector<uint8_t> v(h.size() / 2);
     for (size_t k = 0; k < v.size(); ++k) v[k] = (uint8_t)std::stoul(h.substr(2 * k, 2), nullptr, 16);
     return v;
@@ -75,7 +76,7 @@ static int run_cases(const char *path) {
         const IcmpIface f = icmp_iface_of(hf);
         const std::vector<uint8_t> bytes = unhex(frame_hex);
         std::unique_ptr<uint8_t[]> block(new uint8_t[bytes.size()]);  // exactly the frame
-        std::memcpy(block.get(), bytes.data(), bytes.size());
+        if (!bytes.empty()) std::memcpy(block.get(), bytes.data(), bytes.size());
         const HeapLoad ld{block.get(), (uint32_t)bytes.size()};
         const IcmpPlan p = icmp_decide(ld, ld.len, (uint32_t)verdict, (uint32_t)code, f);
         CHECK(p.status == status);

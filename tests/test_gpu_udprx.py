@@ -191,6 +191,119 @@ def test_batch_sizes(oracle, n, cap):
     assert (e.deliver_frame[int(e.counts[0]):] == C.NO_FRAME).all() and int(e.counts[0]) < n
 
 
+# ---- several steps of the scan: more than 65,536 frames ----------------------------------------
+
+SCAN_STEP = 256 * 256        # frames per step of the one-workgroup scan: 256 tiles of 256 frames
+SCAN_KINDS = ("listener", "assoc", "unreach", "nothing")
+
+
+def _scan_batches(oracle):
+    """Two batches of two whole steps of the scan and a part of a third (3 tiles and 77 frames),
+    of 42- to 60-byte frames, with eight listeners and 64 associations. Steps 0 and 2: deliveries
+    (to a listener and to an association in turn) and unreach requests, alternating, in the
+    step's first and last tile (so on both sides of both step boundaries), at lanes 0 and 63 of a
+    wave, at a tile's first and last frame and at every 97th frame; the second batch swaps
+    deliveries and requests, so that every such place sees both. Step 1: every frame is delivered
+    (first batch), every frame asks for an unreach and none is delivered (second batch). The
+    other frames: ARP, a datagram for another host, one with a bad checksum, a broadcast nobody
+    takes.
+    The frames come from a pool of a few dozen distinct ones, so the model runs on the pool and
+    its per-frame answers are spread over the batch by index (the model treats every frame on its
+    own; the lists are the frame numbers in order); the first and the last 600 frames of each
+    batch are checked against the model run on them directly.
+    [(frames, Expected)], interface, association table, listener table."""
+    if "scan" not in _cache:
+        n = 2 * SCAN_STEP + 3 * 256 + 77
+        ifc, lis, tbl = C.iface(), C.bit_listeners(LIS, 8), C.many_assocs(KEY, 64)
+        kinds = {
+            "listener": [C.dgram(7000 + k % 8, n=k % 19) for k in range(16)],
+            "assoc": [C.dgram(6000 + j % 7, dst=R.NONLOCAL if j % 3 == 2 else R.LOCAL, src=R.PEER + 1 + j,
+                              sport=30000 + j % 11, n=j % 19) for j in range(64)],
+            "unreach": [C.dgram(9 + k, n=k % 19, pad60=bool(k & 1)) for k in range(16)],
+            "nothing": [F.LOCAL_MAC + F.peer_mac(1) + b"\x08\x06" + bytes(46), C.dgram(9, dst=R.NONLOCAL, n=5),
+                        C.dgram(7003, chk="bad", n=7), C.dgram(7001, dst=R.BCAST, n=18)],
+        }
+        pool, first, count = [], [], []
+        for name in SCAN_KINDS:
+            first.append(len(pool))
+            count.append(len(kinds[name]))
+            pool += kinds[name]
+        first, count = np.array(first), np.array(count)
+        assert {len(f) for f in pool} <= set(range(42, 61)) and {42, 60} <= {len(f) for f in pool}
+        v = _verdicts(oracle, pool)
+        pe = C.expected(pool, v, ifc, tbl, lis, DGRAM)
+        taken = np.zeros(len(pool), dtype=bool)
+        taken[pe.deliver_frame[:int(pe.counts[0])].astype(np.int64)] = True
+        k0, k1, k2, k3 = (slice(first[q], first[q] + count[q]) for q in range(4))
+        assert taken[k0].all() and pe.dgrams["listeners"][k0].all() and (pe.dgrams["assoc"][k0] == C.NO_ASSOC).all()
+        assert taken[k1].all() and (pe.dgrams["assoc"][k1] != C.NO_ASSOC).all() and not pe.dgrams["listeners"][k1].any()
+        assert (pe.unreach[k2] == C.PORT_UNREACH).all() and not taken[k2].any()
+        assert (pe.unreach[k3] == C.NO_UNREACH).all() and not taken[k3].any() and set(v[k3]) == {0, 5, 6}
+        assert (pe.unreach[k0] == C.NO_UNREACH).all() and (pe.unreach[k1] == C.NO_UNREACH).all()
+        special = np.zeros(n, dtype=bool)
+        for step in (0, 2):
+            lo, hi = step * SCAN_STEP, min((step + 1) * SCAN_STEP, n)
+            special[lo:hi:97] = True
+            for edge in (lo, hi - 256 if hi - lo >= 512 else hi - 77):
+                special[[edge, min(edge + 63, hi - 1), min(edge + 64, hi - 1), min(edge + 255, hi - 1)]] = True
+            special[[lo + 255, lo + 256, hi - 1]] = True
+        pos = np.flatnonzero(special)
+        k, i = np.arange(pos.size), np.arange(n)
+        batches = []
+        for b in (0, 1):
+            kind = np.full(n, 3)
+            kind[pos] = np.where((k + b) & 1, 2, (k >> 1) & 1)
+            kind[SCAN_STEP:2 * SCAN_STEP] = i[:SCAN_STEP] & 1 if b == 0 else 2
+            idx = first[kind] + i % count[kind]
+            frames = [pool[j] for j in idx]
+            e = C.Expected()
+            e.verdict, e.dgrams, e.unreach = v[idx].copy(), pe.dgrams[idx].copy(), pe.unreach[idx].copy()
+            rows = np.flatnonzero(taken[idx])
+            e.deliver_frame = np.full(n, C.NO_FRAME, dtype=np.uint64)
+            e.deliver_frame[:rows.size] = rows
+            e.counts = np.array([rows.size, int((e.unreach != C.NO_UNREACH).sum())], dtype=np.uint64)
+            for part in (slice(0, 600), slice(n - 600, n)):
+                d = C.expected(frames[part], e.verdict[part], ifc, tbl, lis, DGRAM)
+                assert d.dgrams.tobytes() == e.dgrams[part].tobytes() and np.array_equal(d.unreach, e.unreach[part])
+                assert np.array_equal(d.deliver_frame[:int(d.counts[0])].astype(np.int64),
+                                      np.flatnonzero(taken[idx][part]))
+            # both kinds in the first and in the last tile of steps 0 and 2, on both sides of each boundary
+            for lo, hi in ((0, 256), (SCAN_STEP - 256, SCAN_STEP), (2 * SCAN_STEP, 2 * SCAN_STEP + 256), (n - 77, n)):
+                assert taken[idx][lo:hi].any() and (e.unreach[lo:hi] != C.NO_UNREACH).any(), (b, lo)
+            batches.append((frames, e))
+        (_, e0), (_, e1) = batches
+        mid = slice(SCAN_STEP, 2 * SCAN_STEP)
+        assert np.array_equal(e0.deliver_frame[e0.deliver_frame.searchsorted(SCAN_STEP):][:SCAN_STEP],
+                              np.arange(SCAN_STEP, 2 * SCAN_STEP, dtype=np.uint64))
+        assert (e0.unreach[mid] == C.NO_UNREACH).all() and (e1.unreach[mid] == C.PORT_UNREACH).all()
+        assert not np.isin(e1.deliver_frame[:int(e1.counts[0])], np.arange(SCAN_STEP, 2 * SCAN_STEP)).any()
+        assert int(e0.counts[0]) > SCAN_STEP and int(e1.counts[1]) > SCAN_STEP
+        assert (e0.dgrams["assoc"][mid] != C.NO_ASSOC).any() and e0.dgrams["listeners"][mid].any()
+        _cache["scan"] = (batches, ifc, tbl, lis)
+    return _cache["scan"]
+
+
+@pytest.mark.parametrize("slotted,cap", [(False, -1), (True, -1), (False, 1)])
+def test_scan_over_several_steps(oracle, slotted, cap):
+    """131,917 frames: the scan's loop runs three times and carries its sums from step to step;
+    the ballots lie behind 517 scanned pairs, and the emit pass adds the tile sums of the second
+    and third step to the ranks it takes from them. Every output is compared whole with the model
+    (numpy comparisons, no loop per frame), between intact guards, the workspace's included."""
+    batches, ifc, tbl, lis = _scan_batches(oracle)
+    _tune("aux_blocks", cap)
+    try:
+        for frames, e in batches:
+            n = len(frames)
+            assert n == 2 * SCAN_STEP + 3 * 256 + 77
+            lay = Layout(frames, slotted, slot=64)
+            out = Guarded(n)
+            got = lay.call(ifc, tbl, lis, out)
+            assert got.n == n
+            _compare(e, out, lay)
+    finally:
+        _tune("aux_blocks", -1)
+
+
 # ---- table sizes --------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("n_lis", [0, 1, 64])
