@@ -1657,6 +1657,161 @@ def udp_rx_demux_slotted(frames, slot_stride: int, lens, iface, assocs=None, lis
                            deliver_frame, counts, workspace, stream)
 
 
+AIPSTACK_ARP_REPLY_HEADER = 42       # Ethernet 14 + ARP 28
+AIPSTACK_ARP_NONE = 27               # arp_rx_respond: shorter than 14 bytes, or EtherType != 0x0806
+AIPSTACK_ARP_MALFORMED = 28          # ARP, but short or with a wrong HwType / ProtoType / length
+AIPSTACK_ARP_SEEN = 29               # a valid ARP packet, no reply due
+AIPSTACK_ARP_REPLY = 30              # a valid ARP packet, reply emitted
+AIPSTACK_ARP_HAVE_ADDR = 1           # iface flag: the interface has an address
+AIPSTACK_ARP_REC_LEARN = 1           # record flags: the sender MAC is not broadcast
+AIPSTACK_ARP_REC_NEW_OK = 2          # an entry for the sender address may be created
+AIPSTACK_ARP_REC_NOTIFY = 4          # the observers are notified
+AIPSTACK_ARP_REC_REPLY = 8           # a reply was emitted
+
+# ``aipstack_arp_iface`` (chksum.h): the receiving interface, host-made.
+ARP_IFACE_DTYPE = np.dtype({
+    "names": ["local_addr", "netmask", "mac", "flags", "reserved"],
+    "formats": ["<u4", "<u4", ("u1", (6,)), "u1", ("u1", (17,))],
+    "offsets": [0, 4, 8, 14, 15],
+    "itemsize": 32,
+})
+# ``aipstack_arp_record`` (chksum.h): what the host's ARP table does with one frame's sender.
+ARP_RECORD_DTYPE = np.dtype({
+    "names": ["sender_addr", "sender_mac", "op", "flags", "status", "reserved"],
+    "formats": ["<u4", ("u1", (6,)), "<u2", "u1", "u1", "<u2"],
+    "offsets": [0, 4, 10, 12, 13, 14],
+    "itemsize": 16,
+})
+assert ARP_IFACE_DTYPE.itemsize == 32 and ARP_RECORD_DTYPE.itemsize == 16
+
+
+def arp_iface(local_addr: int, netmask: int, mac, *, have_addr: bool = True) -> np.ndarray:
+    """One ``ARP_IFACE_DTYPE`` record (address and mask in host byte order, ``mac``: 6 bytes;
+    ``have_addr=False``: an interface without an address, as before DHCP has one)."""
+    f = np.zeros(1, dtype=ARP_IFACE_DTYPE)
+    f["local_addr"], f["netmask"] = local_addr, netmask
+    f["flags"] = AIPSTACK_ARP_HAVE_ADDR if have_addr else 0
+    f["mac"][0] = np.frombuffer(bytes(mac), dtype=np.uint8)
+    return f
+
+
+def arp_rx_respond_workspace_bytes(n: int) -> int:
+    """``aipstack_arp_rx_respond_workspace_bytes``: the workspace :func:`arp_rx_respond` needs for
+    n frames."""
+    return int(_lib.load().aipstack_arp_rx_respond_workspace_bytes(max(n, 0)))
+
+
+class ArpResponses:
+    """What :func:`arp_rx_respond` leaves (device tensors, n frames): ``status`` (uint8:
+    AIPSTACK_ARP_*), ``records`` (uint8, n * 16 bytes: n ``aipstack_arp_record`` records),
+    ``headers`` (uint8, n slots of ``hdr_stride`` bytes; slot i holds frame i's reply),
+    ``hdr_lens`` (int32: 42 or 0), ``chunk_index`` (int64, n + 1, all zero: a reply has no chunk),
+    ``reply_frame`` / ``seen_frame`` (int64, n: the frame indices of the replies and of the valid
+    ARP packets in frame order, -1 beyond the count) and ``counts`` (int64, 2: replies, seen).
+    ``chunk_addr`` / ``chunk_len`` are empty, which makes the object a ``segments`` argument of
+    :func:`tx_linearise` / :func:`tx_linearise_slotted` (a frame without a reply is skipped)."""
+
+    def __init__(self, headers, hdr_stride, hdr_lens, chunk_index, status, records, reply_frame,
+                 seen_frame, counts):
+        torch = _torch()
+        self.headers, self.hdr_stride, self.hdr_lens = headers, hdr_stride, hdr_lens
+        self.chunk_index, self.status, self.records = chunk_index, status, records
+        self.reply_frame, self.seen_frame, self.counts = reply_frame, seen_frame, counts
+        self.chunk_addr = torch.empty(0, dtype=torch.int64, device=headers.device)
+        self.chunk_len = torch.empty(0, dtype=torch.int32, device=headers.device)
+
+    @property
+    def n(self) -> int:
+        return self.chunk_index.numel() - 1
+
+    def records_numpy(self) -> np.ndarray:
+        """The records on the host as an ``ARP_RECORD_DTYPE`` array (synchronises)."""
+        return self.records[:self.n * 16].cpu().numpy().view(ARP_RECORD_DTYPE)
+
+
+_ARP_OUTS = (("hdr_lens", 4, 1, 0), ("chunk_index", 8, 1, 1), ("status", 1, 1, 0), ("records", 1, 16, 0),
+             ("reply_frame", 8, 1, 0), ("seen_frame", 8, 1, 0))
+
+
+def _arp_call(name, frames, where, n, iface, hdr_stride, headers, workspace, out, stream):
+    """What the two ARP entry points share: the outputs (fresh, or those of ``out``), the
+    workspace, the call `name` on n frames laid out by `where`."""
+    torch = _torch()
+    lib = _lib.load()
+    f = np.ascontiguousarray(iface, dtype=ARP_IFACE_DTYPE).reshape(-1)
+    if f.size != 1:
+        raise ValueError("iface must be one ARP_IFACE_DTYPE record")
+    dev = frames.device
+    if out is not None:
+        headers, hdr_stride = out.headers, out.hdr_stride
+    if headers is None:
+        headers = torch.zeros(max(n, 1) * hdr_stride, dtype=torch.uint8, device=dev)
+    _require_device(headers, "headers")
+    _same_device(frames, headers, "frames and headers")
+    if headers.element_size() != 1 or hdr_stride <= 0 or headers.numel() < n * hdr_stride:
+        raise ValueError("headers must be a uint8 device tensor of n whole slots of hdr_stride bytes")
+    sizes = [(k, size, n * per + extra) for k, size, per, extra in _ARP_OUTS] + [("counts", 8, 2)]
+    if out is None:
+        dt = {1: torch.uint8, 4: torch.int32, 8: torch.int64}
+        outs = {k: torch.empty(count, dtype=dt[size], device=dev) for k, size, count in sizes}
+    else:
+        outs = {k: getattr(out, k) for k, _, _ in sizes}
+        for k, size, count in sizes:
+            t = outs[k]
+            _require_device(t, f"out.{k}")
+            _same_device(frames, t, f"frames and out.{k}")
+            if t.element_size() != size or t.numel() != count:
+                raise ValueError(f"out.{k} must hold {count} {size}-byte elements")
+    res = ArpResponses(headers, hdr_stride, outs["hdr_lens"], outs["chunk_index"], outs["status"],
+                       outs["records"], outs["reply_frame"], outs["seen_frame"], outs["counts"])
+    if n == 0:  # nothing to launch: the index's one entry and the counts are 0, every other output is empty
+        res.chunk_index.zero_()
+        res.counts.zero_()
+        return res
+    workspace, ws_bytes = _workspace(workspace, arp_rx_respond_workspace_bytes(n), frames, "frames")
+    launch_stream = _launch_stream(stream, dev)
+    _check(getattr(lib, name)(
+        frames.data_ptr(), *where, n, f.ctypes.data, res.status.data_ptr(), res.records.data_ptr(),
+        headers.data_ptr(), hdr_stride, res.hdr_lens.data_ptr(), res.chunk_index.data_ptr(),
+        res.reply_frame.data_ptr(), res.seen_frame.data_ptr(), res.counts.data_ptr(),
+        workspace.data_ptr(), ws_bytes, _stream_handle(launch_stream)), name)
+    workspace.record_stream(launch_stream)
+    return res
+
+
+def arp_rx_respond(frames, offsets, iface, *, hdr_stride: int = 64, headers=None, workspace=None,
+                   out=None, stream=None) -> ArpResponses:
+    """ARP on receive on the GPU (``aipstack_arp_rx_respond``): frame i =
+    ``frames[offsets[i]:offsets[i+1]]``, all received on the interface ``iface`` (an
+    ``ARP_IFACE_DTYPE`` record, :func:`arp_iface`). Every frame gets its status and its
+    ``aipstack_arp_record`` (the sender's address and MAC, and what the host's ARP table and the
+    observers do with them); a request for the interface's address gets its 42-byte reply in slot
+    i of the header ring, addressed to the ARP sender hardware address. No Rx verify runs (ARP
+    carries no checksum) and at most the first 42 bytes of a frame are read. ``headers``: the ring
+    to write (device uint8 tensor of at least n slots of ``hdr_stride`` bytes; else a fresh,
+    zeroed one); ``out``: an :class:`ArpResponses` whose tensors are reused; ``workspace``: a
+    device tensor of at least :func:`arp_rx_respond_workspace_bytes` bytes, 8-byte aligned.
+    Returns an :class:`ArpResponses` (chksum.h has the rules and the byte layout). With no frame
+    at all nothing runs: ``chunk_index`` (one entry) and ``counts`` are set to 0 and the header
+    ring is left as it is."""
+    _require_device(frames, "frames")
+    _require_offsets(offsets)
+    _same_device(frames, offsets, "frames and offsets")
+    n = max(offsets.numel() - 1, 0)
+    return _arp_call("aipstack_arp_rx_respond", frames, (offsets.data_ptr(),), n, iface, hdr_stride,
+                     headers, workspace, out, stream)
+
+
+def arp_rx_respond_slotted(frames, slot_stride: int, lens, iface, *, hdr_stride: int = 64,
+                           headers=None, workspace=None, out=None, stream=None) -> ArpResponses:
+    """:func:`arp_rx_respond` on a ring of frame slots (frame i = the lens[i] bytes at
+    ``frames[i*slot_stride:]``, as :func:`rx_verify_slotted`)."""
+    _require_device(frames, "frames")
+    n = _require_lens(lens, frames.numel() * frames.element_size(), slot_stride, frames)
+    return _arp_call("aipstack_arp_rx_respond_slotted", frames, (slot_stride, lens.data_ptr()), n,
+                     iface, hdr_stride, headers, workspace, out, stream)
+
+
 class SplitFrames:
     """What :func:`split_frames` returns (host arrays): ``headers`` (n slots of ``hdr_stride``
     bytes), ``hdr_lens`` (uint32), ``payload`` (uint8, every chunk's bytes) and ``chunks``

@@ -934,6 +934,114 @@ int aipstack_udp_rx_demux_slotted(const void *d_base, uint64_t slot_stride, cons
                                   uint64_t *d_counts, void *d_workspace, uint64_t workspace_bytes,
                                   void *stream);
 
+/* ---- ARP on receive: replies and sender mappings of a batch of frames ---------------------- */
+
+/* The other branch of EthIpIface::recvFrame (eth/EthIpIface.h:367-390): recvArpPacket (:474-508)
+ * with the address tests of save_hw_addr / get_arp_entry (:587-627, :664-698) and the reply of
+ * send_arp_packet (:774-803), for a batch of frames in device memory. Every frame that Rx verify
+ * calls AIPSTACK_RX_DROP_NOT_IP4 because its EtherType is 0x0806 gets a 16-byte record that says
+ * what the host's ARP table has to do with its sender, and a request for the interface's address
+ * gets its 42-byte reply as a header slot without any chunk, which aipstack_tx_linearise turns
+ * into a frame. ARP carries no checksum, so these calls do not run Rx verify.
+ * Stays with the host: the ARP table itself (the LRU list, weak and hard entries, recycling,
+ * timers, the Query and Refreshing states, the retry lists, resolve_hw_addr and the requests it
+ * sends) and the observers' callbacks. */
+#define AIPSTACK_ARP_REPLY_HEADER 42u /* Ethernet 14 + ARP 28 */
+#define AIPSTACK_ARP_NONE       27  /* per frame: shorter than 14 bytes, or EtherType != 0x0806 (:370, :387) */
+#define AIPSTACK_ARP_MALFORMED  28  /* ARP, but shorter than 14 + 28 (:477), or HwType != 1, ProtoType !=
+                                       0x0800, HwAddrLen != 6 or ProtoAddrLen != 4 (:483-489) */
+#define AIPSTACK_ARP_SEEN       29  /* a valid ARP packet, no reply due */
+#define AIPSTACK_ARP_REPLY      30  /* a valid ARP packet, reply emitted */
+#define AIPSTACK_ARP_HAVE_ADDR  1u  /* iface flag: the interface has an address (getIp4Addrs() != nullptr) */
+#define AIPSTACK_ARP_REC_LEARN  1u  /* the sender MAC is not ff:ff:ff:ff:ff:ff: save_hw_addr goes on to
+                                       get_arp_entry (:590) */
+#define AIPSTACK_ARP_REC_NEW_OK 2u  /* get_arp_entry may create an entry for the sender address (:675-698) */
+#define AIPSTACK_ARP_REC_NOTIFY 4u  /* the observers are notified (:622) */
+#define AIPSTACK_ARP_REC_REPLY  8u  /* a reply was emitted (status AIPSTACK_ARP_REPLY) */
+
+typedef struct aipstack_arp_iface {  /* 32 bytes, host-made, host byte order; HOST memory */
+    uint32_t local_addr;   /* m_addr.addr; not looked at without AIPSTACK_ARP_HAVE_ADDR */
+    uint32_t netmask;      /* m_addr.netmask; netaddr = local_addr & netmask and bcastaddr =
+                              netaddr | ~netmask, as IpIface::setIp4Addr derives them */
+    uint8_t  mac[6];       /* the interface's MAC: Ethernet source and sender of the replies */
+    uint8_t  flags;        /* AIPSTACK_ARP_HAVE_ADDR */
+    uint8_t  reserved[17]; /* 0 */
+} aipstack_arp_iface;
+
+typedef struct aipstack_arp_record {  /* 16 bytes; all zero but `status` for _ARP_NONE / _ARP_MALFORMED */
+    uint32_t sender_addr;   /* SrcProtoAddr, host byte order */
+    uint8_t  sender_mac[6]; /* SrcHwAddr, as on the wire */
+    uint16_t op;            /* OpType as received, host byte order (any value; only 1 is looked at) */
+    uint8_t  flags;         /* AIPSTACK_ARP_REC_* */
+    uint8_t  status;        /* AIPSTACK_ARP_*: d_status[i] */
+    uint16_t reserved;      /* 0 */
+} aipstack_arp_record;
+
+/* The batch (frames as aipstack_chksum_rx_verify / _rx_verify_slotted take them, under the same
+ * offsets, span and slot contracts, a slot's length clamped to min(slot_stride, 65535)) comes
+ * from one interface, h_iface (HOST memory, read before the call returns). Of a frame at most
+ * the first 42 bytes are read, and never a byte past the frame's own length.
+ * Per frame i, with the ARP fields at frame bytes 14-41:
+ *   - d_status[i]: AIPSTACK_ARP_NONE / _MALFORMED / _SEEN / _REPLY as defined above.
+ *   - d_arp[i]: the record. For _SEEN / _REPLY, with ip = sender_addr:
+ *       LEARN   sender_mac is not all-ones;
+ *       NEW_OK  ip is neither all-ones nor zero, AIPSTACK_ARP_HAVE_ADDR is set, (ip & netmask) ==
+ *               netaddr and ip != bcastaddr: what get_arp_entry asks of an address it has no
+ *               entry for. It is set whatever LEARN says. The host applies a LEARN record as
+ *               "an entry for ip was found, or NEW_OK": then the entry becomes Valid with
+ *               sender_mac (:599-616);
+ *       NOTIFY  LEARN and ip is neither all-ones nor zero, with or without an interface address
+ *               (DHCP's case, :618-626);
+ *       REPLY   the status is _REPLY.
+ *   - a reply is due (:500-506) when OpType == 1, AIPSTACK_ARP_HAVE_ADDR is set and DstProtoAddr
+ *     == local_addr, whatever LEARN says. Its 42 bytes (send_arp_packet(Reply, src_mac,
+ *     src_ip_addr)) go to d_hdr + i*hdr_stride: Ethernet destination = the ARP sender hardware
+ *     address (not the frame's Ethernet source), Ethernet source = mac, EtherType 0x0806; HwType
+ *     1, ProtoType 0x0800, HwAddrLen 6, ProtoAddrLen 4, OpType 2, SrcHwAddr = mac, SrcProtoAddr =
+ *     local_addr, DstHwAddr / DstProtoAddr = the request's sender. The slot's bytes [42,
+ *     min(hdr_stride, 64)) are written as 0 (a 64-byte ring on a 64-byte boundary is stored in
+ *     whole lines), bytes past 64 are untouched; the slot of a frame without a reply is
+ *     untouched. No padding to 60 bytes (the reference sends 42).
+ *   - d_hdr_len[i]: 42 for a reply, else 0 (aipstack_tx_linearise skips such a segment).
+ *   - d_reply_frame: n entries: the frame indices of the replies in frame order, the entries at
+ *     and beyond the count written as ~0;
+ *   - d_seen_frame: n entries: the indices of the frames with status _SEEN or _REPLY in frame
+ *     order (the records the host's table loop visits), the tail written as ~0;
+ *   - d_counts[2]: [0] the number of replies, [1] the number of seen frames;
+ *   - d_chunk_index[0..n]: n+1 entries, all written as 0: a reply has no chunk. d_hdr, hdr_stride,
+ *     d_hdr_len and d_chunk_index go to aipstack_tx_linearise / _slotted as they are (d_status may
+ *     be its d_seg_status); for its d_chunk_addr and d_chunk_len the caller passes any non-null
+ *     pointers, for instance d_chunk_index itself: with an index of zeros no entry of either
+ *     array is ever read.
+ * Every output is written for all n frames in every call, and outputs depend on inputs only.
+ * Stream-ordered launches through the caller's workspace (8-byte aligned, at least
+ * aipstack_arp_rx_respond_workspace_bytes(n) = 16 * (ceil(n / 256) + 1) + 64 * ceil(n / 256)
+ * bytes, free again once the stream passes the call): a decide pass (one frame per lane: the
+ * frame's bytes 10-33 and 38-41 at its own alignment, d_status, d_arp, per wave the 64-bit ballots of
+ * replies and of seen frames, per 256-frame tile their counts); a scan of the tile counts by one
+ * workgroup; an emit pass (the lists from the ballots, each reply from the record just written,
+ * d_hdr_len, d_chunk_index, the tails). No kernel waits for another workgroup. Never allocates or
+ * synchronises; can be captured into a graph and repeated. _EINVAL before any work for a null
+ * pointer, hdr_stride < 42, a flag bit other than AIPSTACK_ARP_HAVE_ADDR, a reserved byte that is
+ * not 0, n > 2^40, d_chunk_index / d_reply_frame / d_seen_frame / d_counts or the workspace not
+ * 8-byte aligned, d_hdr_len or d_arp not 4-byte aligned (d_arp on a 16-byte boundary is stored in
+ * whole lines), a short workspace, a slot stride outside (0, AIPSTACK_CHKSUM_MAX_SLOT_STRIDE];
+ * n == 0 is a no-op. */
+uint64_t aipstack_arp_rx_respond_workspace_bytes(uint64_t n);
+int aipstack_arp_rx_respond(const void *d_base, const uint64_t *d_offsets, uint64_t n,
+                            const aipstack_arp_iface *h_iface, uint8_t *d_status,
+                            aipstack_arp_record *d_arp, void *d_hdr, uint64_t hdr_stride,
+                            uint32_t *d_hdr_len, uint64_t *d_chunk_index, uint64_t *d_reply_frame,
+                            uint64_t *d_seen_frame, uint64_t *d_counts, void *d_workspace,
+                            uint64_t workspace_bytes, void *stream);
+int aipstack_arp_rx_respond_slotted(const void *d_base, uint64_t slot_stride, const uint32_t *d_len,
+                                    uint64_t n, const aipstack_arp_iface *h_iface,
+                                    uint8_t *d_status, aipstack_arp_record *d_arp, void *d_hdr,
+                                    uint64_t hdr_stride, uint32_t *d_hdr_len,
+                                    uint64_t *d_chunk_index, uint64_t *d_reply_frame,
+                                    uint64_t *d_seen_frame, uint64_t *d_counts, void *d_workspace,
+                                    uint64_t workspace_bytes, void *stream);
+
 /* ---- 3. host-memory streaming engine ----------------------------------------------- */
 
 /* The reference's packet path starts and ends in host memory (TAP read()/write(),
