@@ -1812,6 +1812,186 @@ def arp_rx_respond_slotted(frames, slot_stride: int, lens, iface, *, hdr_stride:
                      iface, hdr_stride, headers, workspace, out, stream)
 
 
+AIPSTACK_TCP_RSP_HEADER = 54         # = AIPSTACK_TCP_SEGMENT_HEADER: an RST is a segment without data
+AIPSTACK_TCP_RSP_NONE = 31           # tcp_rx_respond: no valid segment record
+AIPSTACK_TCP_RSP_NOT_LOCAL = 32      # the destination is not the interface's address
+AIPSTACK_TCP_RSP_PCB = 33            # a PCB was found: the host calls pcb_input
+AIPSTACK_TCP_RSP_DROP = 34           # no PCB (or an RST requested), nothing sent
+AIPSTACK_TCP_RSP_SYN = 35            # a listener matched a pure SYN with an acceptable MSS
+AIPSTACK_TCP_RSP_RST = 36            # an RST was emitted
+AIPSTACK_TCP_NO_LISTENER = 0xFFFFFFFF
+AIPSTACK_TCP_MAX_LISTENERS = 256
+
+# ``aipstack_tcp_listener`` (chksum.h): one entry of the listener table, in list order.
+TCP_LISTENER_DTYPE = np.dtype({
+    "names": ["addr", "port", "reserved0", "cookie", "reserved1"],
+    "formats": ["<u4", "<u2", "<u2", "<u4", "<u4"],
+    "offsets": [0, 4, 6, 8, 12],
+    "itemsize": 16,
+})
+assert TCP_LISTENER_DTYPE.itemsize == 16
+
+
+def tcp_listeners(entries) -> np.ndarray:
+    """A ``TCP_LISTENER_DTYPE`` table from ``(addr, port, cookie)`` triples (addr in host byte
+    order, 0 = any), in the order given: the order the reference walks its listener list, newest
+    first."""
+    entries = list(entries)
+    t = np.zeros(len(entries), dtype=TCP_LISTENER_DTYPE)
+    for k, (addr, port, cookie) in enumerate(entries):
+        t[k]["addr"], t[k]["port"], t[k]["cookie"] = addr, port, cookie
+    return t
+
+
+def tcp_rx_respond_workspace_bytes(n: int) -> int:
+    """``aipstack_tcp_rx_respond_workspace_bytes``: the workspace :func:`tcp_rx_respond` needs for
+    n frames."""
+    return int(_lib.load().aipstack_tcp_rx_respond_workspace_bytes(max(n, 0)))
+
+
+class TcpResponses:
+    """What :func:`tcp_rx_respond` leaves (device tensors, n frames): ``verdict`` (uint8), ``segs``
+    (uint8, n * 32 bytes) and ``pcb`` (int32) as :func:`tcp_rx_parse` writes them; ``status``
+    (uint8: AIPSTACK_TCP_RSP_*); ``listener`` (int32: the matched listener's cookie, bit pattern of
+    ``AIPSTACK_TCP_NO_LISTENER`` = -1 where none was consulted and matched); ``headers`` (uint8, n
+    slots of ``hdr_stride`` bytes; slot i holds frame i's RST), ``hdr_lens`` (int32: 54 or 0),
+    ``chunk_index`` (int64, n + 1, all zero: an RST has no chunk); ``response_frame`` /
+    ``syn_frame`` (int64, n: the frame indices of the RSTs and of the ``_RSP_SYN`` frames in frame
+    order, -1 beyond the count) and ``counts`` (int64, 2: RSTs, SYNs). ``chunk_addr`` /
+    ``chunk_len`` are empty, which makes the object a ``segments`` argument of
+    :func:`tx_linearise` / :func:`tx_linearise_slotted` (a frame without an RST is skipped)."""
+
+    def __init__(self, headers, hdr_stride, outs):
+        torch = _torch()
+        self.headers, self.hdr_stride = headers, hdr_stride
+        for k, t in outs.items():
+            setattr(self, k, t)
+        self.chunk_addr = torch.empty(0, dtype=torch.int64, device=headers.device)
+        self.chunk_len = torch.empty(0, dtype=torch.int32, device=headers.device)
+
+    @property
+    def n(self) -> int:
+        return self.chunk_index.numel() - 1
+
+    def segs_numpy(self) -> np.ndarray:
+        """The records on the host as a ``TCP_RX_SEG_DTYPE`` array (synchronises)."""
+        return self.segs[:self.n * 32].cpu().numpy().view(TCP_RX_SEG_DTYPE)
+
+    def pcb_numpy(self) -> np.ndarray:
+        """The PCB cookies on the host as uint32 (synchronises)."""
+        return self.pcb[:self.n].cpu().numpy().view(np.uint32)
+
+    def listener_numpy(self) -> np.ndarray:
+        """The listener cookies on the host as uint32 (synchronises)."""
+        return self.listener[:self.n].cpu().numpy().view(np.uint32)
+
+
+# name, element size, elements per frame, extra elements
+_TCP_RSP_OUTS = (("verdict", 1, 1, 0), ("segs", 1, 32, 0), ("pcb", 4, 1, 0), ("status", 1, 1, 0),
+                 ("listener", 4, 1, 0), ("hdr_lens", 4, 1, 0), ("chunk_index", 8, 1, 1),
+                 ("response_frame", 8, 1, 0), ("syn_frame", 8, 1, 0))
+
+
+def _tcp_rsp_call(name, frames, where, n, iface, tcp_ttl, pcbs, listeners, rst_request, hdr_stride,
+                  headers, workspace, out, stream):
+    """What the two entry points share: the outputs (fresh, or those of ``out``), the tables
+    (uploaded on the launch stream), the workspace, the call `name` on n frames laid out by
+    `where`."""
+    torch = _torch()
+    lib = _lib.load()
+    f = np.ascontiguousarray(iface, dtype=ICMP_IFACE_DTYPE).reshape(-1)
+    if f.size != 1:
+        raise ValueError("iface must be one ICMP_IFACE_DTYPE record")
+    dev = frames.device
+    if out is not None:
+        headers, hdr_stride = out.headers, out.hdr_stride
+    if headers is None:
+        headers = torch.zeros(max(n, 1) * hdr_stride, dtype=torch.uint8, device=dev)
+    _require_device(headers, "headers")
+    _same_device(frames, headers, "frames and headers")
+    if headers.element_size() != 1 or hdr_stride <= 0 or headers.numel() < n * hdr_stride:
+        raise ValueError("headers must be a uint8 device tensor of n whole slots of hdr_stride bytes")
+    sizes = [(k, size, n * per + extra) for k, size, per, extra in _TCP_RSP_OUTS] + [("counts", 8, 2)]
+    if out is None:
+        dt = {1: torch.uint8, 4: torch.int32, 8: torch.int64}
+        outs = {k: torch.empty(count, dtype=dt[size], device=dev) for k, size, count in sizes}
+    else:
+        outs = {k: getattr(out, k) for k, _, _ in sizes}
+        for k, size, count in sizes:
+            t = outs[k]
+            _require_device(t, f"out.{k}")
+            _same_device(frames, t, f"frames and out.{k}")
+            if t.element_size() != size or t.numel() != count:
+                raise ValueError(f"out.{k} must hold {count} {size}-byte elements")
+    if rst_request is not None:
+        _require_device(rst_request, "rst_request")
+        _same_device(frames, rst_request, "frames and rst_request")
+        if rst_request.element_size() != 1 or rst_request.numel() < n:
+            raise ValueError("rst_request must be a uint8 device tensor with >= n elements")
+    res = TcpResponses(headers, hdr_stride, outs)
+    launch_stream = _launch_stream(stream, dev)
+    with torch.cuda.stream(launch_stream):  # an upload is ordered before the call
+        pp, pn, pkeep = _udp_table(pcbs, TCP_PCB_KEY_DTYPE, "pcbs", frames)
+        lp, ln, lkeep = _udp_table(listeners, TCP_LISTENER_DTYPE, "listeners", frames)
+        if n == 0:  # nothing to launch: the index's one entry and the counts are 0, the rest is empty
+            res.chunk_index.zero_()
+            res.counts.zero_()
+            return res
+    workspace, ws_bytes = _workspace(workspace, tcp_rx_respond_workspace_bytes(n), frames, "frames")
+    _check(getattr(lib, name)(
+        frames.data_ptr(), *where, n, f.ctypes.data, tcp_ttl, pp, pn, lp, ln,
+        rst_request.data_ptr() if rst_request is not None else None, res.verdict.data_ptr(),
+        res.segs.data_ptr(), res.pcb.data_ptr(), res.status.data_ptr(), res.listener.data_ptr(),
+        headers.data_ptr(), hdr_stride, res.hdr_lens.data_ptr(), res.chunk_index.data_ptr(),
+        res.response_frame.data_ptr(), res.syn_frame.data_ptr(), res.counts.data_ptr(),
+        workspace.data_ptr(), ws_bytes, _stream_handle(launch_stream)), name)
+    workspace.record_stream(launch_stream)
+    for keep, given in ((pkeep, pcbs), (lkeep, listeners)):
+        if keep is not None and keep is not given:
+            keep.record_stream(launch_stream)
+    return res
+
+
+def tcp_rx_respond(frames, offsets, iface, pcbs=None, listeners=None, rst_request=None, *,
+                   tcp_ttl: int = 64, hdr_stride: int = 64, headers=None, workspace=None, out=None,
+                   stream=None) -> TcpResponses:
+    """Rx verify, the TCP parse and the answer to segments without a connection on the GPU
+    (``aipstack_tcp_rx_respond``): frame i = ``frames[offsets[i]:offsets[i+1]]``, all received on
+    the interface ``iface`` (an ``ICMP_IFACE_DTYPE`` record, :func:`icmp_iface`; its ``ttl`` is
+    the ICMP one and is not used: ``tcp_ttl`` is the RSTs'). ``verdict``, ``segs`` and ``pcb`` are
+    what :func:`tcp_rx_parse` gives with the same ``pcbs``; ``status`` says what is left for the
+    host: ``pcb_input`` (``_RSP_PCB``), the rest of ``listen_input`` for the listener whose cookie
+    is in ``listener`` (``_RSP_SYN``), or nothing. ``listeners``: at most 256
+    ``TCP_LISTENER_DTYPE`` entries (:func:`tcp_listeners`), newest first as the reference walks
+    them; the first match wins. Each table: a host array (uploaded on the launch stream), a device
+    uint8 tensor already resident, or ``None``. ``rst_request``: a uint8 device tensor, nonzero
+    where the host wants an RST whatever the tables say; ``None`` = no requests. RST j in frame
+    order carries the Ident ``ip_id + j`` and lies in slot i of the header ring. ``headers``,
+    ``out`` (a :class:`TcpResponses` whose tensors are reused) and ``workspace``
+    (:func:`tcp_rx_respond_workspace_bytes` bytes) as for :func:`arp_rx_respond`. Returns a
+    :class:`TcpResponses` (chksum.h has the rules and the byte layout). With no frame at all
+    nothing runs: ``chunk_index`` (one entry) and ``counts`` are set to 0 and the header ring is
+    left as it is."""
+    _require_device(frames, "frames")
+    _require_offsets(offsets)
+    _same_device(frames, offsets, "frames and offsets")
+    n = max(offsets.numel() - 1, 0)
+    return _tcp_rsp_call("aipstack_tcp_rx_respond", frames, (offsets.data_ptr(),), n, iface, tcp_ttl,
+                         pcbs, listeners, rst_request, hdr_stride, headers, workspace, out, stream)
+
+
+def tcp_rx_respond_slotted(frames, slot_stride: int, lens, iface, pcbs=None, listeners=None,
+                           rst_request=None, *, tcp_ttl: int = 64, hdr_stride: int = 64,
+                           headers=None, workspace=None, out=None, stream=None) -> TcpResponses:
+    """:func:`tcp_rx_respond` on a ring of frame slots (frame i = the lens[i] bytes at
+    ``frames[i*slot_stride:]``, as :func:`rx_verify_slotted`)."""
+    _require_device(frames, "frames")
+    n = _require_lens(lens, frames.numel() * frames.element_size(), slot_stride, frames)
+    return _tcp_rsp_call("aipstack_tcp_rx_respond_slotted", frames, (slot_stride, lens.data_ptr()),
+                         n, iface, tcp_ttl, pcbs, listeners, rst_request, hdr_stride, headers,
+                         workspace, out, stream)
+
+
 class SplitFrames:
     """What :func:`split_frames` returns (host arrays): ``headers`` (n slots of ``hdr_stride``
     bytes), ``hdr_lens`` (uint32), ``payload`` (uint8, every chunk's bytes) and ``chunks``

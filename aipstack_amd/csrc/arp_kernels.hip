@@ -34,16 +34,7 @@ namespace {
 static_assert(kArpTile == kBlock && kArpTileWaves == kBlock / kWave, "one tile per block iteration");
 constexpr int kWaves = kBlock / kWave;
 
-// Where the ballots lie behind the counts: wave w of tile t has its pair at [2 * (4 t + w)].
-__device__ __forceinline__ uint64_t ballots_at(uint64_t tiles) { return 2u * (tiles + 1u); }
-
-// A ballot, the same in every lane of the wave, in scalar registers. (uniform64 of lane_pass.h
-// is for indices: readfirstlane gives an int, and a low word with bit 31 set would extend into
-// the high one.)
-__device__ __forceinline__ uint64_t uniform_bits(uint64_t v) {
-    return (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(v >> 32)) << 32 |
-           (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)v);
-}
+// (where the ballots lie behind the counts, and how a wave reads one: pair_scan.h)
 
 // LINES: d_arp is stored in whole lines (16-byte aligned).
 template <class Frames, bool LINES>

@@ -63,6 +63,19 @@ __global__ __launch_bounds__(kBlock) void pair_scan_kernel(uint64_t tiles, uint6
     }
 }
 
+// For the callers that also leave each wave's ballots behind the counts (arp_kernels.hip,
+// tcprsp_kernels.hip): a pair of 64-bit ballots per wave, four waves per tile; wave w of tile t
+// has its pair at [2 * (4 t + w)] behind the tiles + 1 pairs of counts.
+__device__ __forceinline__ uint64_t ballots_at(uint64_t tiles) { return 2u * (tiles + 1u); }
+
+// A ballot, the same in every lane of the wave, in scalar registers. (uniform64 of lane_pass.h
+// is for indices: readfirstlane gives an int, and a low word with bit 31 set would extend into
+// the high one.)
+__device__ __forceinline__ uint64_t uniform_bits(uint64_t v) {
+    return (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(v >> 32)) << 32 |
+           (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)v);
+}
+
 }  // namespace
 }  // namespace aipstack_amd
 

@@ -547,8 +547,8 @@ int aipstack_udp_tx_fragment(const aipstack_udp_dgram *d_dgrams, const uint64_t 
  * and find the PCB by address tuple (find_pcb, tcp/IpTcpProto.h:806-820, ordered by
  * TcpPcbKeyCompare::CompareKeys, tcp/TcpPcbKey.h:50-86) -- for a batch of frames in device
  * memory. The host's Rx loop becomes "for each record with a PCB: pcb_input(pcb, meta, data)".
- * The TCP state machine, listeners, RST replies and the local-address / unicast-source checks
- * (they need interface state) stay with the host. */
+ * The TCP state machine stays with the host; listeners, RST replies and the local-address /
+ * unicast-source checks (they need interface state) are aipstack_tcp_rx_respond's, below. */
 #define AIPSTACK_RX_DROP_TCP_OFFSET 11      /* TCP checksum good, data offset outside
                                                [20, datagram length] (IpTcpProto_input.h:108-116) */
 #define AIPSTACK_TCP_NO_PCB 0xFFFFFFFFu
@@ -1041,6 +1041,149 @@ int aipstack_arp_rx_respond_slotted(const void *d_base, uint64_t slot_stride, co
                                     uint64_t *d_chunk_index, uint64_t *d_reply_frame,
                                     uint64_t *d_seen_frame, uint64_t *d_counts, void *d_workspace,
                                     uint64_t workspace_bytes, void *stream);
+
+/* ---- TCP without a connection: listener match and RST replies of a batch of frames -------- */
+
+/* What the reference does with a TCP datagram around find_pcb, short of pcb_input and of the
+ * PCB allocation in listen_input: the local-address test in front (tcp/IpTcpProto_input.h:72),
+ * and for a segment without a PCB checkUnicastSrcAddr (:139, ip/IpStack.h:839-843),
+ * find_listener_for_rx (:145, tcp/IpTcpProto.h:824-837), the flag and MSS tests at the top of
+ * listen_input (:372-401, CalcTcpSndMss, tcp/TcpMiscUtils.h:55-67) and the RST of
+ * send_rst_reply / send_rst / send_tcp_nodata (tcp/IpTcpProto_output.h:989-1018, :1338-1404)
+ * -- for a batch of frames in device memory. These calls do Rx verify, everything
+ * aipstack_tcp_rx_parse does (the same d_verdict, d_segs and d_pcb, byte for byte), and then
+ * decide per frame: the host calls pcb_input (_RSP_PCB), the host continues listen_input at
+ * "check maximum number of PCBs" (:383, _RSP_SYN), nothing happens, or an RST leaves. The RST is
+ * a 54-byte segment without data, emitted as a header slot without any chunk, which
+ * aipstack_tx_linearise turns into a frame. The host's TCP receive loop becomes "for each
+ * _RSP_PCB frame: pcb_input; for each _RSP_SYN frame: the rest of listen_input".
+ * Stays with the host: everything in listen_input from :383 on (the PCB count, allocation, the
+ * ISS, the SYN-ACK; a SYN the host then refuses gets its RST through d_rst_request in a later
+ * call), pcb_input, the next hop of the reply (routing and ARP: the RST's Ethernet destination is
+ * the received frame's source MAC and the host may overwrite those six bytes), segments that
+ * aipstack_ip4_rx_reassemble completes (a fragment never gets an answer here), and more than
+ * AIPSTACK_TCP_MAX_LISTENERS listeners. */
+#define AIPSTACK_TCP_RSP_HEADER 54u       /* = AIPSTACK_TCP_SEGMENT_HEADER: Ethernet 14 + IPv4 20 + TCP 20 */
+#define AIPSTACK_TCP_RSP_NONE       31    /* per frame: no valid segment record (not accepted as TCP, or
+                                             AIPSTACK_RX_DROP_TCP_OFFSET) */
+#define AIPSTACK_TCP_RSP_NOT_LOCAL  32    /* valid record, dst != local_addr (:72: dropped, PCB or not) */
+#define AIPSTACK_TCP_RSP_PCB        33    /* dst local, PCB found, no RST requested: the host calls pcb_input */
+#define AIPSTACK_TCP_RSP_DROP       34    /* dst local, no PCB (or an RST requested), nothing sent */
+#define AIPSTACK_TCP_RSP_SYN        35    /* a listener matched a pure SYN with an acceptable MSS */
+#define AIPSTACK_TCP_RSP_RST        36    /* an RST was emitted */
+#define AIPSTACK_TCP_NO_LISTENER 0xFFFFFFFFu
+#define AIPSTACK_TCP_MAX_LISTENERS 256u
+
+typedef struct aipstack_tcp_listener {  /* 16 bytes; DEVICE table, in the order the reference walks
+                                           m_listeners_list (listenIp4 prepends: newest first) */
+    uint32_t addr;       /* the listener's address, host byte order; 0 = any */
+    uint16_t port;
+    uint16_t reserved0;  /* ignored */
+    uint32_t cookie;     /* the caller's listener handle */
+    uint32_t reserved1;  /* ignored */
+} aipstack_tcp_listener;
+
+/* The batch (frames as aipstack_chksum_rx_verify / _rx_verify_slotted take them, under the same
+ * offsets, span and slot contracts) comes from one interface. h_iface: HOST memory, read before
+ * the call returns, validated as aipstack_icmp_rx_respond validates it; used here: local_addr,
+ * bcast_addr, mtu, ip_id, mac. Its ttl is the ICMP TTL and is not used: tcp_ttl (1..255, the
+ * reference's TcpTTL, default 64) is the RSTs' TTL. d_pcbs / n_pcbs: the sorted key table of
+ * aipstack_tcp_rx_parse, under the same contract. d_listeners / n_listeners: at most
+ * AIPSTACK_TCP_MAX_LISTENERS entries in DEVICE memory, 8-byte aligned, read once per workgroup
+ * into LDS; only addr, port and cookie influence the result (reserved0 travels with the port's
+ * load and is masked off, reserved1 is never loaded; n_listeners == 0: no table, d_listeners may
+ * be NULL);
+ * the first entry in table order with port == dst port && (addr == dst || addr == 0) wins.
+ * d_rst_request: NULL, or n bytes; nonzero = the host wants send_rst_reply for frame i whatever
+ * the tables say (a SYN it refused in an earlier pass: m_num_pcbs >= m_max_pcbs, allocate_pcb
+ * failed), the counterpart of d_unreach_code.
+ *
+ * Per frame i, with src / dst the received IPv4 addresses and flags the record's OffsetFlags:
+ *   d_verdict[i], d_segs[i], d_pcb[i]   what aipstack_tcp_rx_parse writes;
+ *   d_status[i]   _RSP_NONE       no valid record;
+ *                 _RSP_NOT_LOCAL  dst != local_addr;
+ *                 _RSP_PCB        a PCB was found and d_rst_request[i] is 0;
+ *                 _RSP_DROP       src is all-ones, multicast ((src & 0xF0000000) == 0xE0000000) or
+ *                                 bcast_addr; or no listener and RST set (:149); or a listener
+ *                                 matched, (flags & 0x17) != 0x02 and (flags & 0x14) != 0x10
+ *                                 (:372-379; SYN+FIN is among these);
+ *                 _RSP_SYN        a listener matched, (flags & 0x17) == 0x02 (SYN without FIN, RST,
+ *                                 ACK), and no MSS option or one >= 216 (MinAllowedMss = MinMTU -
+ *                                 40; mtu - 40 >= 216 always). The options are those of the record;
+ *                 _RSP_RST        the source passes and: d_rst_request[i] != 0 (no listener is
+ *                                 consulted); or no listener and RST clear; or a listener matched,
+ *                                 (flags & 0x17) != 0x02 and (flags & 0x14) == 0x10; or a listener
+ *                                 matched a pure SYN whose MSS option is below 216.
+ *   d_listener[i] the matched entry's cookie where a listener was consulted and matched (_RSP_SYN,
+ *                 and the _RSP_DROP / _RSP_RST cases behind a match), else AIPSTACK_TCP_NO_LISTENER.
+ *
+ * The RST's 54 bytes, for the j-th RST in frame order:
+ *   Ethernet  destination = the frame's source MAC, source = mac, EtherType 0x0800;
+ *   IPv4      (sendIp4Dgram, ip/IpStack.h:423-453) 0x4500 (IHL 5 whatever options the segment
+ *             carried), total length 40, Ident ip_id + j mod 2^16, flags / offset 0x4000
+ *             (TcpIpSendFlags = DF), TTL tcp_ttl, protocol 6, source = dst, destination = src, the
+ *             header checksum;
+ *   TCP       ports swapped; with ACK in flags: seq = the segment's ack_num, ack 0, OffsetFlags
+ *             0x5004 (RST); else seq 0, ack = seq_num + data_len + ((flags & 0x03) != 0) mod 2^32,
+ *             OffsetFlags 0x5014 (RST|ACK); data_len is the record's (Ethernet padding is not
+ *             data); window 0, urgent 0; the checksum over pseudo-header and header, stored as
+ *             computed (a computed 0 stays 0x0000).
+ * The ICMP and the TCP responder each take a start Ident: the host gives the second call ip_id +
+ * the first call's response count. The reference draws both from one counter (m_next_id) in frame
+ * order, so within a batch its Idents interleave differently; an Ident only has to be unique per
+ * (source, destination, protocol) while a datagram may be in flight, RSTs carry DF and are never
+ * fragmented, and each value is still used once.
+ *
+ * Outputs, all written for all n frames in every call (outputs depend on inputs only):
+ *   header slots   an RST's 54 bytes at d_hdr + i*hdr_stride (hdr_stride >= 54), the slot's bytes
+ *                  [54, min(hdr_stride, 64)) written as 0 (a 64-byte ring on a 64-byte boundary is
+ *                  stored in whole lines), bytes past 64 untouched; the slot of a frame without an
+ *                  RST is untouched;
+ *   d_hdr_len[i]   54 for an RST, else 0 (aipstack_tx_linearise skips such a segment);
+ *   d_chunk_index  n+1 entries, all written as 0: an RST has no chunk. d_hdr, hdr_stride, d_hdr_len
+ *                  and d_chunk_index go to aipstack_tx_linearise / _slotted as ARP's replies do;
+ *   d_response_frame  n entries: the frame indices of the RSTs in frame order, the entries at and
+ *                  beyond the count written as ~0;
+ *   d_syn_frame    the same for the _RSP_SYN frames;
+ *   d_counts[2]    [0] the number of RSTs, [1] the number of _RSP_SYN frames.
+ *
+ * Stream-ordered launches through the caller's workspace (8-byte aligned, at least
+ * aipstack_tcp_rx_respond_workspace_bytes(n) = 16 * (ceil(n / 256) + 1) + 64 * ceil(n / 256)
+ * bytes, free again once the stream passes the call): Rx verify, unchanged; a decide pass (one
+ * frame per lane: of a frame accepted as TCP at most the first 134 header bytes, never past the
+ * frame's own length; status, record, pcb and listener; per wave the ballots of RSTs and SYNs,
+ * per 256-frame tile their counts); a scan of the tile counts by one workgroup; an emit pass (the
+ * lists from the ballots, each RST from the record just written and the frame's bytes 6-11,
+ * d_hdr_len, d_chunk_index, the tails). No kernel waits for another workgroup. Never allocates or
+ * synchronises; can be captured into a graph and repeated. _EINVAL before any work for a null
+ * pointer other than d_rst_request and the two tables when their count is 0, n or n_pcbs above
+ * 2^40, n_listeners > AIPSTACK_TCP_MAX_LISTENERS, tcp_ttl outside 1..255, an interface
+ * aipstack_icmp_rx_respond rejects, hdr_stride < 54, d_segs / d_pcbs / d_listeners /
+ * d_chunk_index / d_response_frame / d_syn_frame / d_counts or the workspace not 8-byte aligned,
+ * d_pcb / d_listener / d_hdr_len not 4-byte aligned, a short workspace, a slot stride outside
+ * (0, AIPSTACK_CHKSUM_MAX_SLOT_STRIDE]; n == 0 is a no-op. */
+uint64_t aipstack_tcp_rx_respond_workspace_bytes(uint64_t n);
+int aipstack_tcp_rx_respond(const void *d_base, const uint64_t *d_offsets, uint64_t n,
+                            const aipstack_icmp_iface *h_iface, uint32_t tcp_ttl,
+                            const aipstack_tcp_pcb_key *d_pcbs, uint64_t n_pcbs,
+                            const aipstack_tcp_listener *d_listeners, uint32_t n_listeners,
+                            const uint8_t *d_rst_request, uint8_t *d_verdict,
+                            aipstack_tcp_rx_seg *d_segs, uint32_t *d_pcb, uint8_t *d_status,
+                            uint32_t *d_listener, void *d_hdr, uint64_t hdr_stride,
+                            uint32_t *d_hdr_len, uint64_t *d_chunk_index,
+                            uint64_t *d_response_frame, uint64_t *d_syn_frame, uint64_t *d_counts,
+                            void *d_workspace, uint64_t workspace_bytes, void *stream);
+int aipstack_tcp_rx_respond_slotted(const void *d_base, uint64_t slot_stride, const uint32_t *d_len,
+                                    uint64_t n, const aipstack_icmp_iface *h_iface, uint32_t tcp_ttl,
+                                    const aipstack_tcp_pcb_key *d_pcbs, uint64_t n_pcbs,
+                                    const aipstack_tcp_listener *d_listeners, uint32_t n_listeners,
+                                    const uint8_t *d_rst_request, uint8_t *d_verdict,
+                                    aipstack_tcp_rx_seg *d_segs, uint32_t *d_pcb, uint8_t *d_status,
+                                    uint32_t *d_listener, void *d_hdr, uint64_t hdr_stride,
+                                    uint32_t *d_hdr_len, uint64_t *d_chunk_index,
+                                    uint64_t *d_response_frame, uint64_t *d_syn_frame,
+                                    uint64_t *d_counts, void *d_workspace, uint64_t workspace_bytes,
+                                    void *stream);
 
 /* ---- 3. host-memory streaming engine ----------------------------------------------- */
 

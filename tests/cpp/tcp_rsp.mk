@@ -1,0 +1,20 @@
+# TCP segments without a connection: the shared decision and RST builder
+# (aipstack_amd/csrc/tcprsp_common.h, on tcprx_common.h) and the host code (tcprsp_host.cpp, plain
+# C++ without a HIP call) in a stand-alone test under AddressSanitizer + UBSan.
+#   make -C tests/cpp -f tcp_rsp.mk        build/asan/tcp_rsp_build_test
+ROCM    ?= /opt/rocm
+ROOT    := ../..
+CSRC    := $(ROOT)/aipstack_amd/csrc
+CLANGXX := $(ROCM)/lib/llvm/bin/clang++
+SAN     := -fsanitize=address,undefined -fno-sanitize-recover=undefined
+
+all: build/asan/tcp_rsp_build_test
+
+build/asan/tcp_rsp_build_test: tcp_rsp_build_test.cpp $(CSRC)/tcprsp_host.cpp $(CSRC)/tcprsp_common.h \
+                               $(CSRC)/tcprx_common.h $(CSRC)/icmp_common.h \
+                               $(ROOT)/include/aipstack_amd/chksum.h
+	@mkdir -p build/asan
+	$(CLANGXX) -g -O1 -fno-omit-frame-pointer -std=c++17 -Wall -Wextra $(SAN) -I$(ROOT)/include -I$(CSRC) \
+	    -o $@ tcp_rsp_build_test.cpp $(CSRC)/tcprsp_host.cpp
+
+.PHONY: all
