@@ -87,6 +87,11 @@ SIGNATURES = {
                                                  _c_vp, _c_u32, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp,
                                                  _c_vp, _c_u64, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp,
                                                  _c_u64, _c_vp]),
+    "aipstack_icmp_rx_unreach_workspace_bytes": (_c_u64, [_c_u64]),
+    "aipstack_icmp_rx_unreach": (_c_int, [_c_vp, _c_vp, _c_u64, _c_vp, _c_vp, _c_u64, _c_vp, _c_vp, _c_vp,
+                                          _c_vp, _c_vp, _c_vp, _c_u64, _c_vp]),
+    "aipstack_icmp_rx_unreach_slotted": (_c_int, [_c_vp, _c_u64, _c_vp, _c_u64, _c_vp, _c_vp, _c_u64, _c_vp,
+                                                  _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_u64, _c_vp]),
     "aipstack_chksum_strerror": (ctypes.c_char_p, [_c_int]),
     "aipstack_chksum_last_hip_error": (_c_int, []),
     "aipstack_chksum_device_check": (_c_int, [_c_int]),

@@ -1992,6 +1992,115 @@ def tcp_rx_respond_slotted(frames, slot_stride: int, lens, iface, pcbs=None, lis
                          workspace, out, stream)
 
 
+AIPSTACK_ICMP_DU_NONE = 37           # icmp_rx_unreach: no Destination Unreachable a handler would see
+AIPSTACK_ICMP_DU_PARSED = 38         # a valid record; the quoted protocol's handler returns at once
+AIPSTACK_ICMP_DU_TCP_NO_PCB = 39     # quoted TCP, code 4, >= 8 quoted bytes: no PCB
+AIPSTACK_ICMP_DU_TCP_PCB = 40        # the same, and the PCB table holds the connection
+
+# ``aipstack_icmp_du_record`` (chksum.h): one parsed Destination Unreachable, host byte order.
+ICMP_DU_RECORD_DTYPE = np.dtype({
+    "names": ["local_addr", "remote_addr", "local_port", "remote_port", "seq", "rest", "pcb", "ip_off",
+              "l4_len", "code", "proto", "ttl", "hl"],
+    "formats": ["<u4", "<u4", "<u2", "<u2", "<u4", "<u4", "<u4", "<u2", "<u2", "u1", "u1", "u1", "u1"],
+    "offsets": [0, 4, 8, 10, 12, 16, 20, 24, 26, 28, 29, 30, 31],
+    "itemsize": 32,
+})
+assert ICMP_DU_RECORD_DTYPE.itemsize == 32
+
+
+def icmp_rx_unreach_workspace_bytes(n: int) -> int:
+    """``aipstack_icmp_rx_unreach_workspace_bytes``: the workspace :func:`icmp_rx_unreach` needs for
+    n frames."""
+    return int(_lib.load().aipstack_icmp_rx_unreach_workspace_bytes(max(n, 0)))
+
+
+class IcmpUnreachParsed:
+    """What :func:`icmp_rx_unreach` leaves (device tensors, n frames): ``verdict`` (uint8: Rx
+    verify's), ``status`` (uint8: AIPSTACK_ICMP_DU_*), ``records`` (uint8, n * 32 bytes: n
+    ``aipstack_icmp_du_record`` records, zero where the status is ``_DU_NONE``), ``pcb_frame``
+    (int64, n: the frame index of the j-th ``_DU_TCP_PCB`` frame, -1 beyond the count) and
+    ``counts`` (int64, 2: ``_DU_TCP_PCB`` frames, valid records)."""
+
+    def __init__(self, verdict, status, records, pcb_frame, counts):
+        self.verdict, self.status, self.records = verdict, status, records
+        self.pcb_frame, self.counts = pcb_frame, counts
+
+    @property
+    def n(self) -> int:
+        return self.verdict.numel()
+
+    def records_numpy(self) -> np.ndarray:
+        """The records on the host as an ``ICMP_DU_RECORD_DTYPE`` array (synchronises)."""
+        return self.records[:self.n * 32].cpu().numpy().view(ICMP_DU_RECORD_DTYPE)
+
+
+def _icmp_unreach_call(name, frames, where, n, iface, pcbs, verdict, status, records, pcb_frame,
+                       counts, workspace, stream):
+    """What the two entry points share: the outputs, the PCB table (uploaded on the launch
+    stream), the workspace, the call `name` on n frames laid out by `where`."""
+    f = np.ascontiguousarray(iface, dtype=ICMP_IFACE_DTYPE).reshape(-1)
+    if f.size != 1:
+        raise ValueError("iface must be one ICMP_IFACE_DTYPE record")
+    res = IcmpUnreachParsed(_u8_out(verdict, n, frames), _udp_out(status, n, 1, "status", frames),
+                            _udp_out(records, n * 32, 1, "records", frames),
+                            _udp_out(pcb_frame, n, 8, "pcb_frame", frames),
+                            _udp_out(counts, 2, 8, "counts", frames))
+    for what in ("records", "pcb_frame", "counts"):
+        t = getattr(res, what)
+        if t.numel() and t.data_ptr() % 8:
+            raise ValueError(f"{what} must be 8-byte aligned")
+    launch_stream = _launch_stream(stream, frames.device)
+    with _torch().cuda.stream(launch_stream):  # an upload is ordered before the call
+        pp, pn, pkeep = _udp_table(pcbs, TCP_PCB_KEY_DTYPE, "pcbs", frames)
+        if pn and pp % 8:
+            raise ValueError("pcbs must be 8-byte aligned")
+        if n == 0:  # nothing to launch: the counts are 0, every other output is empty
+            res.counts.zero_()
+            return res
+    workspace, ws_bytes = _workspace(workspace, icmp_rx_unreach_workspace_bytes(n), frames, "frames")
+    _check(getattr(_lib.load(), name)(
+        frames.data_ptr(), *where, n, f.ctypes.data, pp, pn, res.verdict.data_ptr(),
+        res.status.data_ptr(), res.records.data_ptr(), res.pcb_frame.data_ptr(),
+        res.counts.data_ptr(), workspace.data_ptr(), ws_bytes, _stream_handle(launch_stream)), name)
+    workspace.record_stream(launch_stream)
+    if pkeep is not None and pkeep is not pcbs:
+        pkeep.record_stream(launch_stream)
+    return res
+
+
+def icmp_rx_unreach(frames, offsets, iface, pcbs=None, *, verdict=None, status=None, records=None,
+                    pcb_frame=None, counts=None, workspace=None, stream=None) -> IcmpUnreachParsed:
+    """Rx verify plus the parse of received ICMP Destination Unreachable messages on the GPU
+    (``aipstack_icmp_rx_unreach``): frame i = ``frames[offsets[i]:offsets[i+1]]``, all received on
+    the interface ``iface`` (an ``ICMP_IFACE_DTYPE`` record, :func:`icmp_iface`). For every message
+    the reference would hand to a protocol handler the ``aipstack_icmp_du_record``: the quoted
+    addresses, ports and sequence number, the ICMP code and ``rest`` (the next-hop MTU is ``rest &
+    0xFFFF``), and for a quoted TCP segment of a frag-needed message (code 4) the cookie of its
+    PCB in ``pcbs`` (a table of ``TCP_PCB_KEY_DTYPE`` entries sorted by
+    :func:`tcp_pcb_table_sort`: a host array, uploaded on the launch stream, a device uint8 tensor
+    already resident, or ``None``). ``pcb_frame`` lists the frames with a PCB in frame order: the
+    host applies the ``snd_una <= seq <= snd_nxt`` test and calls ``handleIcmpPacketTooBig`` for
+    those alone. Returns an :class:`IcmpUnreachParsed` (chksum.h has the rules)."""
+    _require_device(frames, "frames")
+    _require_offsets(offsets)
+    _same_device(frames, offsets, "frames and offsets")
+    n = max(offsets.numel() - 1, 0)
+    return _icmp_unreach_call("aipstack_icmp_rx_unreach", frames, (offsets.data_ptr(),), n, iface,
+                              pcbs, verdict, status, records, pcb_frame, counts, workspace, stream)
+
+
+def icmp_rx_unreach_slotted(frames, slot_stride: int, lens, iface, pcbs=None, *, verdict=None,
+                            status=None, records=None, pcb_frame=None, counts=None, workspace=None,
+                            stream=None) -> IcmpUnreachParsed:
+    """:func:`icmp_rx_unreach` on a ring of frame slots (frame i = the lens[i] bytes at
+    ``frames[i*slot_stride:]``, as :func:`rx_verify_slotted`)."""
+    _require_device(frames, "frames")
+    n = _require_lens(lens, frames.numel() * frames.element_size(), slot_stride, frames)
+    return _icmp_unreach_call("aipstack_icmp_rx_unreach_slotted", frames,
+                              (slot_stride, lens.data_ptr()), n, iface, pcbs, verdict, status,
+                              records, pcb_frame, counts, workspace, stream)
+
+
 class SplitFrames:
     """What :func:`split_frames` returns (host arrays): ``headers`` (n slots of ``hdr_stride``
     bytes), ``hdr_lens`` (uint32), ``payload`` (uint8, every chunk's bytes) and ``chunks``

@@ -1185,6 +1185,104 @@ int aipstack_tcp_rx_respond_slotted(const void *d_base, uint64_t slot_stride, co
                                     uint64_t *d_counts, void *d_workspace, uint64_t workspace_bytes,
                                     void *stream);
 
+/* ---- ICMP Destination Unreachable on receive: the quoted header and its TCP PCB ------------ */
+
+/* The one ICMP type the reference acts on that aipstack_icmp_rx_respond reports as
+ * AIPSTACK_ICMP_NONE: Destination Unreachable (type 3). recvIcmp4Dgram runs its source and
+ * destination tests (ip/IpStack.h:1093-1148), handleIcmp4DestUnreach parses the IPv4 header quoted
+ * inside the message (:1192-1249) and calls the handler of the quoted protocol; TCP's reads the
+ * quoted ports and sequence number and calls find_pcb (tcp/IpTcpProto_input.h:154-182), UDP's is
+ * empty. All of that is stateless; these calls do it for a batch of frames in device memory, so
+ * that the host's handling of ICMP errors becomes "for each entry of d_pcb_frame: take that
+ * record, apply the snd_una <= seq <= snd_nxt test and call handleIcmpPacketTooBig(remote_addr,
+ * rest & 0xFFFF)" without reading a frame byte.
+ * Stays with the host: canOutput(), the snd_una / snd_nxt window and con == nullptr
+ * (tcp/IpTcpProto_input.h:186-193); the path-MTU cache and its max(MinMTU, mtu) / interface-MTU
+ * clamp (ip/IpPathMtuCache.h:210-250); the requeue and the retransmission; a second interface;
+ * messages that aipstack_ip4_rx_reassemble completes: a fragment (verdict 3) gets no record. */
+#define AIPSTACK_ICMP_DU_NONE        37  /* per frame: no Destination Unreachable a handler would see */
+#define AIPSTACK_ICMP_DU_PARSED      38  /* a valid record; the quoted protocol's handler returns at once */
+#define AIPSTACK_ICMP_DU_TCP_NO_PCB  39  /* quoted TCP, code 4, >= 8 quoted L4 bytes: find_pcb finds nothing */
+#define AIPSTACK_ICMP_DU_TCP_PCB     40  /* the same, and the PCB table holds the connection */
+
+typedef struct aipstack_icmp_du_record {  /* 32 bytes, host byte order; all zero unless hl != 0 */
+    uint32_t local_addr, remote_addr;   /* quoted IPv4 source, destination (IpRxInfoIp4 src_addr, dst_addr):
+                                           the quoted source side is ours */
+    uint16_t local_port, remote_port;   /* quoted L4 bytes 0-1, 2-3; 0 unless l4_len >= 8 (any protocol) */
+    uint32_t seq;                       /* quoted L4 bytes 4-7; 0 unless l4_len >= 8 */
+    uint32_t rest;                      /* ICMP header bytes 4-7, big-endian (Ip4DestUnreachMeta::icmp_rest);
+                                           the next-hop MTU is rest & 0xFFFF (Icmp4GetMtuFromRest) */
+    uint32_t pcb;                       /* the PCB's cookie, else AIPSTACK_TCP_NO_PCB */
+    uint16_t ip_off;                    /* offset of the quoted IPv4 header from the frame start */
+    uint16_t l4_len;                    /* dgram_initial.tot_len; the quoted L4 bytes lie at ip_off + hl */
+    uint8_t  code;                      /* ICMP code (Ip4DestUnreachMeta::icmp_code) */
+    uint8_t  proto, ttl, hl;            /* quoted protocol, TTL, header length (20..60) */
+} aipstack_icmp_du_record;
+
+/* The batch (frames as aipstack_chksum_rx_verify / _rx_verify_slotted take them, under the same
+ * offsets, span and slot contracts) comes from one interface, h_iface (HOST memory, read before
+ * the call returns; validated as aipstack_icmp_rx_respond validates it; only local_addr and
+ * bcast_addr are used here). d_pcbs: n_pcbs aipstack_tcp_pcb_key entries in DEVICE memory under
+ * the contract of aipstack_tcp_rx_parse: sorted by aipstack_tcp_pcb_table_sort, keys unique
+ * (n_pcbs == 0: no table, d_pcbs may be NULL); an unsorted table gives unspecified pcb values (and
+ * with them unspecified _DU_TCP_PCB / _DU_TCP_NO_PCB statuses, list entries and d_counts[0]),
+ * never an access outside the table.
+ * Per frame i (src / dst = the outer IPv4 addresses, hl / total = the outer header and total
+ * length):
+ *   1. the outer tests (recvIcmp4Dgram): Rx verify's verdict is AIPSTACK_RX_ACCEPT and the
+ *      protocol is 1 (so ICMP has at least 8 bytes and a good checksum, :1116, :1127, and the
+ *      frame is not a fragment); src is not all-ones, not multicast ((src & 0xF0000000) ==
+ *      0xE0000000) and not bcast_addr (checkUnicastSrcAddr, :838-843); dst is local_addr,
+ *      bcast_addr or all-ones (:1103-1113; AllowBroadcastPing gates only the echo reply, :1140);
+ *      the ICMP type is 3 (the code is not tested here).
+ *   2. the quoted header (handleIcmp4DestUnreach): icmp_data = IP-payload bytes [8, total - hl)
+ *      (Ethernet padding is not data) has at least 20 bytes (:1196); its version nibble is 4
+ *      (:1210); header_len = 4 * IHL is at least 20 and at most len(icmp_data) (:1217); the quoted
+ *      total length is at least header_len (:1224). l4_len = min(len(icmp_data), quoted total
+ *      length) - header_len (:1235). No other test is made: not of the quoted source against
+ *      local_addr, not of the quoted fragment field, not of the quoted checksum.
+ *   3. a frame that passes 1 and 2 gets the record above and a status other than _DU_NONE; every
+ *      other frame gets 32 zero bytes and _DU_NONE.
+ *   4. the TCP lookup: only for quoted protocol 6, code 4 (DestUnreachFragNeeded) and l4_len >= 8
+ *      the table is searched for {local_addr, remote_addr, local_port, remote_port} of the record:
+ *      _DU_TCP_PCB with pcb = the entry's cookie when found, _DU_TCP_NO_PCB otherwise. Every other
+ *      valid record is _DU_PARSED with pcb = AIPSTACK_TCP_NO_PCB.
+ * Outputs, all written for all n frames in every call (outputs depend on inputs only):
+ *   d_verdict[i]   Rx verify's verdict, unchanged;
+ *   d_status[i]    AIPSTACK_ICMP_DU_*;
+ *   d_records[i]   the record, or 32 zero bytes;
+ *   d_pcb_frame    n entries: the indices of the _DU_TCP_PCB frames in frame order, the entries at
+ *                  and beyond the count written as ~0;
+ *   d_counts[2]    [0] the number of _DU_TCP_PCB frames, [1] the number of valid records.
+ * Stream-ordered launches through the caller's workspace (8-byte aligned, at least
+ * aipstack_icmp_rx_unreach_workspace_bytes(n) = 16 * (ceil(n / 256) + 1) + 32 * ceil(n / 256)
+ * bytes, free again once the stream passes the call): Rx verify, unchanged; a decide pass (one
+ * frame per lane: of a frame accepted as ICMP at most the first 150 bytes, 14 + 60 + 8 + 60 + 8,
+ * never past the frame's own length; the table searched from that lane, every index inside it;
+ * the statuses and the records; per 256-frame block the two counts and the bits of the frames
+ * with a PCB); a scan of the block counts by one workgroup; an emit pass (d_pcb_frame and its
+ * tail). No kernel waits for another workgroup. Never allocates or synchronises; can be captured
+ * into a graph and repeated. _EINVAL before any work for a null pointer (but d_pcbs with n_pcbs
+ * == 0), n or n_pcbs above 2^40, an interface aipstack_icmp_rx_respond rejects, d_records /
+ * d_pcb_frame / d_counts / d_pcbs / the workspace not 8-byte aligned, a short workspace, a slot
+ * stride outside (0, AIPSTACK_CHKSUM_MAX_SLOT_STRIDE]; n == 0 is a no-op. */
+uint64_t aipstack_icmp_rx_unreach_workspace_bytes(uint64_t n);
+int aipstack_icmp_rx_unreach(const void *d_base, const uint64_t *d_offsets, uint64_t n,
+                             const aipstack_icmp_iface *h_iface,
+                             const aipstack_tcp_pcb_key *d_pcbs, uint64_t n_pcbs,
+                             uint8_t *d_verdict, uint8_t *d_status,
+                             aipstack_icmp_du_record *d_records, uint64_t *d_pcb_frame,
+                             uint64_t *d_counts, void *d_workspace, uint64_t workspace_bytes,
+                             void *stream);
+int aipstack_icmp_rx_unreach_slotted(const void *d_base, uint64_t slot_stride,
+                                     const uint32_t *d_len, uint64_t n,
+                                     const aipstack_icmp_iface *h_iface,
+                                     const aipstack_tcp_pcb_key *d_pcbs, uint64_t n_pcbs,
+                                     uint8_t *d_verdict, uint8_t *d_status,
+                                     aipstack_icmp_du_record *d_records, uint64_t *d_pcb_frame,
+                                     uint64_t *d_counts, void *d_workspace,
+                                     uint64_t workspace_bytes, void *stream);
+
 /* ---- 3. host-memory streaming engine ----------------------------------------------- */
 
 /* The reference's packet path starts and ends in host memory (TAP read()/write(),
