@@ -92,6 +92,11 @@ SIGNATURES = {
                                           _c_vp, _c_vp, _c_vp, _c_u64, _c_vp]),
     "aipstack_icmp_rx_unreach_slotted": (_c_int, [_c_vp, _c_u64, _c_vp, _c_u64, _c_vp, _c_vp, _c_u64, _c_vp,
                                                   _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_u64, _c_vp]),
+    "aipstack_arp_table_sort": (_c_int, [_c_vp, _c_u64]),
+    "aipstack_tx_resolve_workspace": (_c_u64, [_c_u64]),
+    "aipstack_tx_resolve": (_c_int, [_c_vp, _c_u64, _c_vp, _c_u64, _c_vp, _c_vp, _c_vp, _c_vp, _c_u32, _c_vp,
+                                     _c_u64, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_u64,
+                                     _c_u32, _c_vp]),
     "aipstack_chksum_strerror": (ctypes.c_char_p, [_c_int]),
     "aipstack_chksum_last_hip_error": (_c_int, []),
     "aipstack_chksum_device_check": (_c_int, [_c_int]),

@@ -2101,6 +2101,197 @@ def icmp_rx_unreach_slotted(frames, slot_stride: int, lens, iface, pcbs=None, *,
                               records, pcb_frame, counts, workspace, stream)
 
 
+AIPSTACK_TX_RES_NONE = 41            # tx_resolve: nothing to resolve for this segment
+AIPSTACK_TX_RES_SENT = 42            # bytes 0..13 of the slot are the Ethernet header
+AIPSTACK_TX_RES_NO_ROUTE = 43        # IpErr::NoIpRoute
+AIPSTACK_TX_RES_BCAST_REJECTED = 44  # IpErr::BroadcastRejected
+AIPSTACK_TX_RES_NONLOCAL_SRC = 45    # IpErr::NonLocalSrc
+AIPSTACK_TX_RES_NO_HW_ROUTE = 46     # IpErr::NoHardwareRoute
+AIPSTACK_TX_RES_ARP_QUERY = 47       # IpErr::ArpQueryInProgress
+AIPSTACK_TX_MAX_IFACES = 16
+AIPSTACK_TX_HAVE_ADDR = 1            # iface flags
+AIPSTACK_TX_HAVE_GATEWAY = 2
+AIPSTACK_TX_ALLOW_BROADCAST = 1      # send flags: IpSendFlags::AllowBroadcastFlag
+AIPSTACK_TX_ALLOW_NONLOCAL_SRC = 2   # IpSendFlags::AllowNonLocalSrc
+AIPSTACK_TX_ROUTE_ANY = 0xFFFF       # force_iface[i]: no interface named
+AIPSTACK_TX_NO_ARP_ENTRY = 0xFFFFFFFF
+AIPSTACK_ARP_STATE_QUERY = 1         # ArpEntryState
+AIPSTACK_ARP_STATE_VALID = 2
+AIPSTACK_ARP_STATE_REFRESHING = 3
+AIPSTACK_TX_ROUTE_GATEWAY = 1        # route flags: next_hop is the gateway
+AIPSTACK_TX_ROUTE_BROADCAST = 2      # the MAC is ff:ff:ff:ff:ff:ff
+AIPSTACK_TX_ROUTE_NEW_ENTRY = 4      # _ARP_QUERY without an entry: the host makes one
+AIPSTACK_TX_ROUTE_FORCED = 8         # the segment named its interface
+
+# ``aipstack_tx_iface`` (chksum.h): one interface of the device table, host byte order.
+TX_IFACE_DTYPE = np.dtype({
+    "names": ["addr", "netmask", "gateway", "prefix", "flags", "mac", "reserved"],
+    "formats": ["<u4", "<u4", "<u4", "u1", "u1", ("u1", (6,)), ("u1", (12,))],
+    "offsets": [0, 4, 8, 12, 13, 14, 20],
+    "itemsize": 32,
+})
+# ``aipstack_arp_entry``: one entry of the ARP table snapshot.
+ARP_ENTRY_DTYPE = np.dtype({
+    "names": ["addr", "iface", "state", "mac", "reserved"],
+    "formats": ["<u4", "<u2", "u1", ("u1", (6,)), ("u1", (3,))],
+    "offsets": [0, 4, 6, 7, 13],
+    "itemsize": 16,
+})
+# ``aipstack_tx_route``: the record of one segment.
+TX_ROUTE_DTYPE = np.dtype({
+    "names": ["next_hop", "arp_index", "iface", "status", "flags", "reserved"],
+    "formats": ["<u4", "<u4", "<u2", "u1", "u1", "<u4"],
+    "offsets": [0, 4, 8, 10, 11, 12],
+    "itemsize": 16,
+})
+assert (TX_IFACE_DTYPE.itemsize, ARP_ENTRY_DTYPE.itemsize, TX_ROUTE_DTYPE.itemsize) == (32, 16, 16)
+
+
+def tx_ifaces(entries) -> np.ndarray:
+    """The interface table of :func:`tx_resolve` as a ``TX_IFACE_DTYPE`` array, from
+    ``(addr or None, prefix, gateway or None, mac)`` per interface **in the order the stack's
+    interface list iterates** (the reference prepends: last constructed first)."""
+    entries = list(entries)
+    t = np.zeros(len(entries), dtype=TX_IFACE_DTYPE)
+    for k, (addr, prefix, gateway, mac) in enumerate(entries):
+        if not 0 <= int(prefix) <= 32 or len(bytes(mac)) != 6:
+            raise ValueError("prefix must be 0..32 and mac 6 bytes")
+        if addr is not None:
+            t[k]["addr"], t[k]["prefix"] = addr, prefix
+            t[k]["netmask"] = (0xFFFFFFFF << (32 - int(prefix))) & 0xFFFFFFFF if prefix else 0
+        if gateway is not None:
+            t[k]["gateway"] = gateway
+        t[k]["flags"] = (AIPSTACK_TX_HAVE_ADDR if addr is not None else 0) | \
+            (AIPSTACK_TX_HAVE_GATEWAY if gateway is not None else 0)
+        t[k]["mac"] = np.frombuffer(bytes(mac), dtype=np.uint8)
+    return t
+
+
+def arp_table_sort(entries):
+    """Host side of :func:`tx_resolve` (``aipstack_arp_table_sort``, no GPU): a copy of ``entries``
+    (an ``ARP_ENTRY_DTYPE`` array) sorted by (iface, addr), the order the lookup searches. Raises
+    :class:`ChksumError` (``AIPSTACK_CHKSUM_EINVAL``) for a duplicate key, a state outside 1..3,
+    an interface index of 16 or more or a nonzero reserved byte."""
+    e = np.array(entries, dtype=ARP_ENTRY_DTYPE).reshape(-1)
+    _check(_lib.load().aipstack_arp_table_sort(e.ctypes.data if e.size else None, e.size),
+           "aipstack_arp_table_sort")
+    return e
+
+
+def tx_resolve_workspace_bytes(n: int) -> int:
+    """``aipstack_tx_resolve_workspace``: the workspace :func:`tx_resolve` needs for n segments."""
+    return int(_lib.load().aipstack_tx_resolve_workspace(max(n, 0)))
+
+
+class TxResolved:
+    """What :func:`tx_resolve` leaves (device tensors, n segments): ``status`` (uint8:
+    AIPSTACK_TX_RES_*), ``routes`` (uint8, n * 16 bytes: n ``aipstack_tx_route`` records),
+    ``send_lens`` (int32, n: the header length for ``_SENT`` and ``_RES_NONE``, else 0: the
+    ``hdr_lens`` to linearise with), ``arp_used`` (uint8, one per ARP entry), ``held_seg`` /
+    ``failed_seg`` (int64, n: the ``_ARP_QUERY`` / the rejected segments in order, -1 beyond the
+    count) and ``counts`` (int64, 2: held, failed)."""
+
+    def __init__(self, status, routes, send_lens, arp_used, held_seg, failed_seg, counts):
+        self.status, self.routes, self.send_lens, self.arp_used = status, routes, send_lens, arp_used
+        self.held_seg, self.failed_seg, self.counts = held_seg, failed_seg, counts
+
+    @property
+    def n(self) -> int:
+        return self.status.numel()
+
+    def routes_numpy(self) -> np.ndarray:
+        """The records on the host as a ``TX_ROUTE_DTYPE`` array (synchronises)."""
+        return self.routes[:self.n * 16].cpu().numpy().view(TX_ROUTE_DTYPE)
+
+
+def _tx_table(table, dtype, name, like):
+    """(pointer, entries, tensor to keep alive) of a device table: None, a device uint8 tensor of
+    whole entries, or a host array of `dtype` (uploaded here)."""
+    torch = _torch()
+    if table is None:
+        return 0, 0, None
+    if not hasattr(table, "data_ptr"):
+        k = np.ascontiguousarray(table, dtype=dtype).reshape(-1)
+        if k.size == 0:
+            return 0, 0, None
+        table = torch.from_numpy(k.view(np.uint8).copy()).to(like.device)
+    _require_device(table, name)
+    _same_device(table, like, f"{name} and headers")
+    nbytes = table.numel() * table.element_size()
+    if nbytes % dtype.itemsize:
+        raise ValueError(f"{name} must hold whole {dtype.itemsize}-byte entries")
+    return (table.data_ptr() if nbytes else 0), nbytes // dtype.itemsize, table
+
+
+def tx_resolve(headers, hdr_stride: int, hdr_lens, ifaces, arp=None, *, seg_status=None,
+               send_flags=None, force_iface=None, status=None, routes=None, send_lens=None,
+               arp_used=None, held_seg=None, failed_seg=None, counts=None, workspace=None,
+               stream=None) -> TxResolved:
+    """Route, permission tests, next-hop MAC and Ethernet header of a batch of Tx header slots on
+    the GPU (``aipstack_tx_resolve``): the batched form of the reference's ``routeIp4`` /
+    ``routeIp4ForceIface``, ``checkSendIp4Allowed`` and ``EthIpIface::driverSendIp4Packet``.
+    Segment i is the ``hdr_lens[i]`` bytes at ``headers[i * hdr_stride:]`` (what the Tx producers
+    and the responders emit); its IPv4 addresses are read and, where it resolves
+    (``AIPSTACK_TX_RES_SENT``), its bytes 0..13 are stored in place. ``ifaces``: the interface
+    table (:func:`tx_ifaces`; a host array, uploaded on the launch stream, or a device uint8
+    tensor); ``arp``: the ARP table snapshot sorted by :func:`arp_table_sort` (the same, or None).
+    ``seg_status`` (uint8), ``send_flags`` (uint8: AIPSTACK_TX_ALLOW_*) and ``force_iface``
+    (int16/uint16: an interface index or AIPSTACK_TX_ROUTE_ANY) are optional device tensors of n
+    entries. Returns a :class:`TxResolved`; pass its ``send_lens`` to :func:`tx_linearise_slotted`
+    as ``hdr_lens`` (chksum.h has the rules)."""
+    torch = _torch()
+    _require_device(headers, "headers")
+    _require_device(hdr_lens, "hdr_lens")
+    _same_device(headers, hdr_lens, "headers and hdr_lens")
+    if hdr_lens.dtype not in (torch.int32, torch.uint32):
+        raise ValueError("hdr_lens must be an int32/uint32 device tensor")
+    n = hdr_lens.numel()
+    if hdr_stride <= 0 or n * hdr_stride > headers.numel() * headers.element_size():
+        raise ValueError("headers must hold n whole slots of hdr_stride bytes")
+    opt = []
+    for t, name, sizes in ((seg_status, "seg_status", (1,)), (send_flags, "send_flags", (1,)),
+                           (force_iface, "force_iface", (2,))):
+        if t is not None:
+            _require_device(t, name)
+            _same_device(headers, t, f"headers and {name}")
+            if t.element_size() not in sizes or t.numel() < n:
+                raise ValueError(f"{name} must hold n {sizes[0]}-byte entries")
+        opt.append(t.data_ptr() if t is not None and n else None)
+    launch_stream = _launch_stream(stream, headers.device)
+    with torch.cuda.stream(launch_stream):  # an upload is ordered before the call
+        ip, n_ifaces, ikeep = _tx_table(ifaces, TX_IFACE_DTYPE, "ifaces", headers)
+        ap, n_arp, akeep = _tx_table(arp, ARP_ENTRY_DTYPE, "arp", headers)
+    if ikeep is None:
+        raise ValueError("ifaces must hold at least one interface")
+    if send_lens is None:
+        send_lens = torch.empty(n, dtype=torch.int32, device=headers.device)
+    else:
+        _require_device(send_lens, "send_lens")
+        if send_lens.dtype not in (torch.int32, torch.uint32) or send_lens.numel() < n:
+            raise ValueError("send_lens must be an int32/uint32 device tensor with >= n elements")
+    res = TxResolved(_udp_out(status, n, 1, "status", headers), _udp_out(routes, n * 16, 1, "routes", headers),
+                     send_lens, _udp_out(arp_used, n_arp, 1, "arp_used", headers),
+                     _udp_out(held_seg, n, 8, "held_seg", headers),
+                     _udp_out(failed_seg, n, 8, "failed_seg", headers),
+                     _udp_out(counts, 2, 8, "counts", headers))
+    if n == 0:  # nothing to launch: no entry was used, the counts are 0
+        res.arp_used.zero_()
+        res.counts.zero_()
+        return res
+    workspace, ws_bytes = _workspace(workspace, tx_resolve_workspace_bytes(n), headers, "headers")
+    _check(_lib.load().aipstack_tx_resolve(
+        headers.data_ptr(), hdr_stride, hdr_lens.data_ptr(), n, *opt, ip, n_ifaces, ap, n_arp,
+        res.status.data_ptr(), res.routes.data_ptr(), res.send_lens.data_ptr(),
+        res.arp_used.data_ptr() if n_arp else None, res.held_seg.data_ptr(),
+        res.failed_seg.data_ptr(), res.counts.data_ptr(), workspace.data_ptr(), ws_bytes, 0,
+        _stream_handle(launch_stream)), "aipstack_tx_resolve")
+    workspace.record_stream(launch_stream)
+    for keep, given in ((ikeep, ifaces), (akeep, arp)):
+        if keep is not None and keep is not given:
+            keep.record_stream(launch_stream)
+    return res
+
+
 class SplitFrames:
     """What :func:`split_frames` returns (host arrays): ``headers`` (n slots of ``hdr_stride``
     bytes), ``hdr_lens`` (uint32), ``payload`` (uint8, every chunk's bytes) and ``chunks``

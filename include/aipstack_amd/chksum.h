@@ -1283,6 +1283,155 @@ int aipstack_icmp_rx_unreach_slotted(const void *d_base, uint64_t slot_stride,
                                      uint64_t *d_counts, void *d_workspace,
                                      uint64_t workspace_bytes, void *stream);
 
+/* ---- Tx resolve: route, permission tests and next-hop MAC of a batch of segments ------------ */
+
+/* The per-packet step between "a header slot holds an IPv4 header" and "the frame may leave":
+ * IpStack::sendIp4Dgram's route (routeIp4, ip/IpStack.h:713-741, or routeIp4ForceIface, :764-780,
+ * when the sender names an interface, as sendIcmp4Message does, :1188) and permission tests
+ * (checkSendIp4Allowed, :666-690), then EthIpIface::driverSendIp4Packet's ARP lookup
+ * (resolve_hw_addr, eth/EthIpIface.h:511-585, with the address tests of get_arp_entry(weak=false),
+ * :635-698) and Ethernet header (:420-430). This call does it for n header slots at once, against
+ * a snapshot of the interfaces and of the ARP tables in device memory.
+ * Stays with the host: the ARP table's life (the LRU order, weak / hard, the timers, the Query /
+ * Refreshing transitions, recycling above NumArpEntries, the retry lists), sending the ARP
+ * requests, IpSendRetryRequest, the MTU test of sendIp4Dgram (:407) and FragmentationNeeded (the
+ * producers fragment), the link state, more than AIPSTACK_TX_MAX_IFACES interfaces. */
+#define AIPSTACK_TX_RES_NONE           41 /* per segment: nothing to resolve (below) */
+#define AIPSTACK_TX_RES_SENT           42 /* bytes 0..13 of the slot are the Ethernet header: IpErr::Success */
+#define AIPSTACK_TX_RES_NO_ROUTE       43 /* IpErr::NoIpRoute */
+#define AIPSTACK_TX_RES_BCAST_REJECTED 44 /* IpErr::BroadcastRejected */
+#define AIPSTACK_TX_RES_NONLOCAL_SRC   45 /* IpErr::NonLocalSrc */
+#define AIPSTACK_TX_RES_NO_HW_ROUTE    46 /* IpErr::NoHardwareRoute */
+#define AIPSTACK_TX_RES_ARP_QUERY      47 /* IpErr::ArpQueryInProgress: the entry is in Query state, or
+                                             there is none and get_arp_entry would make one */
+#define AIPSTACK_TX_MAX_IFACES 16u
+#define AIPSTACK_TX_HAVE_ADDR    1u /* iface flag: m_have_addr */
+#define AIPSTACK_TX_HAVE_GATEWAY 2u /* iface flag: m_have_gateway */
+#define AIPSTACK_TX_ALLOW_BROADCAST    1u /* d_send_flags[i]: IpSendFlags::AllowBroadcastFlag */
+#define AIPSTACK_TX_ALLOW_NONLOCAL_SRC 2u /* d_send_flags[i]: IpSendFlags::AllowNonLocalSrc */
+#define AIPSTACK_TX_ROUTE_ANY 0xFFFFu     /* d_force_iface[i]: no interface named, routeIp4 */
+#define AIPSTACK_TX_NO_ARP_ENTRY 0xFFFFFFFFu
+#define AIPSTACK_ARP_STATE_QUERY      1u  /* aipstack_arp_entry.state: the values of ArpEntryState */
+#define AIPSTACK_ARP_STATE_VALID      2u  /* (eth/EthIpIface.h:228); a Free entry is not in the table */
+#define AIPSTACK_ARP_STATE_REFRESHING 3u
+#define AIPSTACK_TX_ROUTE_GATEWAY   1u /* route flag: next_hop is the interface's gateway */
+#define AIPSTACK_TX_ROUTE_BROADCAST 2u /* route flag: the MAC is ff:ff:ff:ff:ff:ff, no entry involved */
+#define AIPSTACK_TX_ROUTE_NEW_ENTRY 4u /* route flag, _ARP_QUERY only: no entry exists; the host makes one
+                                          in Query state and broadcasts the first request (:566-577) */
+#define AIPSTACK_TX_ROUTE_FORCED    8u /* route flag: the segment named its interface */
+
+typedef struct aipstack_tx_iface {  /* 32 bytes, host byte order; DEVICE table, 4-byte aligned, in the
+                                       order m_iface_list iterates (last constructed first, IpIface.h:97) */
+    uint32_t addr;                  /* m_addr.addr; ignored without _HAVE_ADDR */
+    uint32_t netmask;               /* m_addr.netmask = PrefixMask(prefix); net and broadcast address are
+                                       derived on the device: addr & netmask, that | ~netmask (:131-133) */
+    uint32_t gateway;               /* m_gateway; ignored without _HAVE_GATEWAY */
+    uint8_t  prefix;                /* m_addr.prefix, 0..32: what routeIp4 compares */
+    uint8_t  flags;                 /* AIPSTACK_TX_HAVE_ADDR | AIPSTACK_TX_HAVE_GATEWAY */
+    uint8_t  mac[6];                /* the interface's MAC: bytes 6..11 of a _SENT slot */
+    uint8_t  reserved[12];
+} aipstack_tx_iface;
+
+typedef struct aipstack_arp_entry { /* 16 bytes, host byte order; DEVICE table, 4-byte aligned */
+    uint32_t addr;                  /* ArpEntry::ip_addr */
+    uint16_t iface;                 /* index into the interface table: whose ARP table this entry is of */
+    uint8_t  state;                 /* AIPSTACK_ARP_STATE_*; >= _VALID resolves (:543) */
+    uint8_t  mac[6];                /* ArpEntry::mac_addr; not read in Query state */
+    uint8_t  reserved[3];
+} aipstack_arp_entry;
+
+typedef struct aipstack_tx_route {  /* 16 bytes, host byte order; all zero for _RES_NONE */
+    uint32_t next_hop;              /* IpRouteInfoIp4::addr: the destination or the gateway; 0 for _NO_ROUTE */
+    uint32_t arp_index;             /* the entry that resolved it (_SENT) or is in Query state
+                                       (_ARP_QUERY), else AIPSTACK_TX_NO_ARP_ENTRY */
+    uint16_t iface;                 /* IpRouteInfoIp4::iface as an index; for _NO_ROUTE the interface the
+                                       segment named, or AIPSTACK_TX_ROUTE_ANY */
+    uint8_t  status;                /* AIPSTACK_TX_RES_* (0 in the all-zero record) */
+    uint8_t  flags;                 /* AIPSTACK_TX_ROUTE_* */
+    uint8_t  reserved[4];
+} aipstack_tx_route;
+
+/* Sorts n entries in HOST memory by (iface, addr), the order the lookup searches, as
+ * aipstack_tcp_pcb_table_sort does for the PCB table. _EINVAL for a null pointer with n != 0,
+ * n >= 2^32 - 1, or when two entries have the same (iface, addr), a state outside 1..3, an iface >=
+ * AIPSTACK_TX_MAX_IFACES or a nonzero reserved byte (the array is sorted either way). */
+int aipstack_arp_table_sort(aipstack_arp_entry *h_entries, uint64_t n);
+
+/* Segment i is the header slot at d_hdr + i * hdr_stride that the producers (aipstack_tcp_tx_segment,
+ * aipstack_udp_tx_fragment), the responders (aipstack_icmp_rx_respond, aipstack_tcp_rx_respond) and
+ * aipstack_chksum_tx_fill_hsplit share, d_hdr_len[i] bytes long. Of it only bytes 12..13 and the IPv4
+ * source and destination address, bytes 26..33, are read, at the slot's own alignment; nothing of
+ * a chunk table is.
+ *   nothing to resolve (_RES_NONE): d_hdr_len[i] < 34, or d_hdr_len[i] > hdr_stride (a length
+ *   aipstack_tx_linearise rejects; no byte outside a slot is ever touched), or bytes 12..13 are not
+ *   08 00 (an ARP reply of aipstack_arp_rx_respond), or d_seg_status (may be NULL) holds
+ *   AIPSTACK_TX_BURST_INVALID or AIPSTACK_TX_DGRAM_INVALID for it (then no slot byte is read).
+ * Every other segment, with src / dst its addresses, flags = d_send_flags[i] (NULL: 0 for all; bits
+ * other than the two above are ignored) and k = d_force_iface[i] (NULL: AIPSTACK_TX_ROUTE_ANY for
+ * all), in the reference's order:
+ *   1. the route. k == _ROUTE_ANY: over the n_ifaces interfaces in table order, an interface
+ *      with an address whose subnet holds dst replaces the best so far if its prefix is longer;
+ *      one that does not hold dst but has a gateway is taken only while nothing is chosen
+ *      (:718-731). next_hop = dst if a subnet matched, else the chosen interface's gateway. Any other
+ *      k: that interface; next_hop = dst if dst is all-ones or in its subnet, else its gateway if
+ *      it has one (:769-777). Nothing chosen, or k >= n_ifaces: _NO_ROUTE.
+ *   2. without _ALLOW_BROADCAST: dst all-ones, or the routed interface has an address and dst is
+ *      its broadcast address: _BCAST_REJECTED (:669-679).
+ *   3. without _ALLOW_NONLOCAL_SRC: the routed interface has no address or src is not it:
+ *      _NONLOCAL_SRC (:681-687).
+ *   4. the table is searched for (routed interface, next_hop). Found (the first test, as in
+ *      get_arp_entry, :650): state >= _VALID is _SENT with the entry's MAC, else _ARP_QUERY.
+ *      Not found: next_hop all-ones is _SENT to ff:ff:ff:ff:ff:ff; zero, or an interface without
+ *      an address, or next_hop outside its subnet is _NO_HW_ROUTE; its broadcast address is _SENT
+ *      to ff:ff:ff:ff:ff:ff; anything else _ARP_QUERY with _ROUTE_NEW_ENTRY (:675-698, :566-583).
+ * d_ifaces: n_ifaces <= AIPSTACK_TX_MAX_IFACES entries in DEVICE memory (n_ifaces == 0: every
+ * segment with something to resolve is _NO_ROUTE). d_arp: n_arp entries in DEVICE memory sorted by
+ * aipstack_arp_table_sort, keys unique (n_arp == 0: d_arp and d_arp_used may be NULL). An
+ * unsorted table or one with duplicate keys gives unspecified outcomes of step 4, never a read
+ * outside [0, n_arp).
+ * Outputs, all stored for all n segments (all n_arp entries) in every call, so outputs depend on
+ * inputs only and the call replays from a graph:
+ *   d_status[i]     AIPSTACK_TX_RES_*;
+ *   d_route[i]      the record (4-byte aligned);
+ *   d_send_len[i]   d_hdr_len[i] for _SENT and _RES_NONE, else 0: passed to aipstack_tx_linearise as
+ *                   its d_hdr_len, held and failed segments are skipped; the caller's d_hdr_len
+ *                   stays intact for the retry after the ARP answer;
+ *   d_arp_used[j]   1 where entry j resolved at least one segment (_SENT through it), else 0: the
+ *                   host makes it hard, moves it in the LRU list and applies the attempts_left ==
+ *                   0 -> Refreshing step (:517-559);
+ *   d_held_seg      n entries: the _ARP_QUERY segments in segment order, ~0 at and beyond the
+ *                   count: the host starts one query per distinct (iface, next_hop) with
+ *                   _ROUTE_NEW_ENTRY and queues the retry;
+ *   d_failed_seg    n entries: the _NO_ROUTE, _BCAST_REJECTED, _NONLOCAL_SRC and _NO_HW_ROUTE
+ *                   segments in segment order, ~0 at and beyond the count;
+ *   d_counts[2]     [0] held, [1] failed segments;
+ *   the header ring, for _SENT only: bytes 0..5 the MAC, 6..11 the routed interface's MAC,
+ *                   12..13 08 00, stored with the widest naturally aligned stores the slot's
+ *                   address allows. No other byte of the ring is stored: no byte of another slot,
+ *                   none from 14 on, none of a slot's slack.
+ * Stream-ordered through the caller's workspace (8-byte aligned, at least
+ * aipstack_tx_resolve_workspace(n) = 16 * (ceil(n / 256) + 1) + 64 * ceil(n / 256) bytes, free again
+ * once the stream passes the call): a memset of d_arp_used; a decide pass (one segment per lane,
+ * the interface table once per workgroup in LDS, the ARP table searched from that lane); a scan
+ * of the 256-segment blocks' counts by one workgroup; an emit pass for the two lists. No kernel
+ * waits for another workgroup. Never allocates or synchronises; can be captured into a graph.
+ * flags: no bit is defined; ignored. _EINVAL before any work for a null pointer (d_seg_status,
+ * d_send_flags, d_force_iface excepted, and d_arp / d_arp_used with n_arp == 0), n_ifaces >
+ * AIPSTACK_TX_MAX_IFACES, hdr_stride == 0, n > 2^40, n_arp >= 2^32 - 1 (arp_index has 32 bits),
+ * d_hdr_len / d_send_len / d_route /
+ * d_ifaces / d_arp not 4-byte aligned, d_force_iface not 2-byte aligned, d_held_seg / d_failed_seg
+ * / d_counts / the workspace not 8-byte aligned, a short workspace. n == 0 returns _OK before
+ * the arguments are looked at. */
+uint64_t aipstack_tx_resolve_workspace(uint64_t n);
+int aipstack_tx_resolve(void *d_hdr, uint64_t hdr_stride, const uint32_t *d_hdr_len, uint64_t n,
+                        const uint8_t *d_seg_status, const uint8_t *d_send_flags,
+                        const uint16_t *d_force_iface, const aipstack_tx_iface *d_ifaces,
+                        uint32_t n_ifaces, const aipstack_arp_entry *d_arp, uint64_t n_arp,
+                        uint8_t *d_status, aipstack_tx_route *d_route, uint32_t *d_send_len,
+                        uint8_t *d_arp_used, uint64_t *d_held_seg, uint64_t *d_failed_seg,
+                        uint64_t *d_counts, void *d_workspace, uint64_t workspace_bytes,
+                        uint32_t flags, void *stream);
+
 /* ---- 3. host-memory streaming engine ----------------------------------------------- */
 
 /* The reference's packet path starts and ends in host memory (TAP read()/write(),
