@@ -207,15 +207,24 @@ class Keeper:
         assert self.entries[(k, hop)][0] == QUERY
         return False
 
-    def heard(self, k, frame):
-        """An ARP frame arrived on interface k: save_hw_addr by the record's flags, as the host
-        does with aipstack_arp_record (arp_cases.record)."""
+    def arp_iface(self, k):
+        """Interface k as arp_cases takes it."""
         f = self.ifaces[k]
-        ifc = dict(local=f["addr"], netmask=f["netmask"], have=f["have"], mac=f["mac"])
-        st, ip, mac, op, flags = AC.record(frame, ifc)
+        return dict(local=f["addr"], netmask=f["netmask"], have=f["have"], mac=f["mac"])
+
+    def learned(self, k, rec):
+        """save_hw_addr for one aipstack_arp_record of interface k, rec = (status, sender
+        address, sender MAC, flags): wherever the record comes from, the model or the device."""
+        st, ip, mac, flags = rec
         if st in (AC.SEEN, AC.REPLY) and flags & AC.LEARN and \
                 ((k, ip) in self.entries or flags & AC.NEW_OK):
-            self.entries[(k, ip)] = (VALID, mac)
+            self.entries[(k, ip)] = (VALID, bytes(mac))
+
+    def heard(self, k, frame):
+        """An ARP frame arrived on interface k: the model's record (arp_cases.record), then
+        what the host does with it."""
+        st, ip, mac, op, flags = AC.record(frame, self.arp_iface(k))
+        self.learned(k, (st, ip, mac, flags))
 
 
 # ---- header slots --------------------------------------------------------------------------------
