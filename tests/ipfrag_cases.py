@@ -297,6 +297,11 @@ def reassemble(e, payload, d, headers=None):
 
 # ---- properties of a batch, from the model alone (no vacuous tests) -----------------------
 
+def count_straddle_odd_first(e):
+    """Fragments of two chunks whose first has an odd length (as tcpseg_cases counts segments)."""
+    return sum(1 for ch in e.frag_chunks if len(ch) == 2 and ch[0][1] & 1)
+
+
 def branches(batch, e=None):
     """Which branches of the loop the batch's valid datagrams take, from the model alone."""
     got = set()
