@@ -843,7 +843,8 @@ int launch_short_runs(const Desc &desc, uint64_t n, uint32_t len, uint16_t *d_ou
 // Gapped column runs (round 5, the default for fixed-length packets at a stride that is a
 // multiple of 16, in device memory): chunks of the largest power of two of packets with
 // <= 12 KiB (at most 16), one per wave, through sum_gapped_column_chunk. Strides from 8 MiB,
-// packets over 32 KiB, small batches and tunable gather = 0 keep the gathered stream.
+// packets over 32 KiB or inside one 16-byte segment, small batches and tunable gather = 0 keep
+// the gathered stream.
 int launch_gapped(const GappedDesc &g, uint64_t n, uint16_t *d_out, uint32_t flags,
                   hipStream_t stream) {
     if (n == 0) return AIPSTACK_CHKSUM_OK;
@@ -853,8 +854,10 @@ int launch_gapped(const GappedDesc &g, uint64_t n, uint16_t *d_out, uint32_t fla
     const uint32_t ns = (rs + g.len + 15u) >> 4;
     Shape sh = pick_shape(n, cus);
     const int gm = tuning().gather.load(std::memory_order_relaxed);
+    // (ns == 1, a packet inside one segment: the reciprocal below would be 2^32, which its 32
+    // bits hold as 0, and every packet of a chunk would be read at the first one's place)
     const bool cols = gm != 0 && g.len > 0 && (g.stride & 15u) == 0 && g.stride < (1u << 23) &&
-                      ns <= 2048u && tuning_stream_windows(4) != 0 &&
+                      ns >= 2u && ns <= 2048u && tuning_stream_windows(4) != 0 &&
                       (!sh.small || tuning().chunk_packets.load(std::memory_order_relaxed) != 0);
     if (!cols) return launch<GappedDesc, false>(g, n, g.len, d_out, flags, stream);
     if (tuning().chunk_packets.load(std::memory_order_relaxed) == 0) {
