@@ -97,6 +97,9 @@ SIGNATURES = {
     "aipstack_tx_resolve": (_c_int, [_c_vp, _c_u64, _c_vp, _c_u64, _c_vp, _c_vp, _c_vp, _c_vp, _c_u32, _c_vp,
                                      _c_u64, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_u64,
                                      _c_u32, _c_vp]),
+    "aipstack_tcp_tx_control_workspace_bytes": (_c_u64, [_c_u64]),
+    "aipstack_tcp_tx_control": (_c_int, [_c_vp, _c_u64, _c_vp, _c_u32, _c_vp, _c_u64, _c_vp, _c_vp, _c_vp,
+                                         _c_vp, _c_vp, _c_u64, _c_vp]),
     "aipstack_chksum_strerror": (ctypes.c_char_p, [_c_int]),
     "aipstack_chksum_last_hip_error": (_c_int, []),
     "aipstack_chksum_device_check": (_c_int, [_c_int]),

@@ -2292,6 +2292,126 @@ def tx_resolve(headers, hdr_stride: int, hdr_lens, ifaces, arp=None, *, seg_stat
     return res
 
 
+AIPSTACK_TCP_CTL_MAX_HEADER = 62     # 54 + MSS 4 + window scale 4
+AIPSTACK_TCP_CTL_EMITTED = 48        # tcp_tx_control: the slot holds the descriptor's segment
+AIPSTACK_TCP_CTL_INVALID = 49        # a reserved field or an unknown option bit is set
+
+# ``aipstack_tcp_ctl`` (chksum.h): one TCP segment without data, host byte order.
+TCP_CTL_DTYPE = np.dtype({
+    "names": ["local_addr", "remote_addr", "local_port", "remote_port", "seq", "ack", "window", "mss",
+              "flags", "options", "wnd_scale", "reserved0", "reserved1"],
+    "formats": ["<u4", "<u4", "<u2", "<u2", "<u4", "<u4", "<u2", "<u2", "u1", "u1", "u1", "u1", "<u4"],
+    "offsets": [0, 4, 8, 10, 12, 16, 20, 22, 24, 25, 26, 27, 28],
+    "itemsize": 32,
+})
+assert TCP_CTL_DTYPE.itemsize == 32
+
+
+def tcp_ctl(entries) -> np.ndarray:
+    """A ``TCP_CTL_DTYPE`` array from one mapping per segment: ``local_addr``, ``remote_addr``,
+    ``local_port``, ``remote_port``, ``seq``, ``ack``, ``window``, ``flags`` (the low byte of
+    OffsetFlags) and, where the segment carries them, ``mss`` and ``wnd_scale`` with their bits in
+    ``options`` (``AIPSTACK_TCP_OPT_MSS`` / ``AIPSTACK_TCP_OPT_WND_SCALE``). A field left out is 0."""
+    entries = list(entries)
+    t = np.zeros(len(entries), dtype=TCP_CTL_DTYPE)
+    for k, e in enumerate(entries):
+        for name, v in e.items():
+            if name not in TCP_CTL_DTYPE.names:
+                raise ValueError(f"aipstack_tcp_ctl has no field {name!r}")
+            t[k][name] = v
+    return t
+
+
+def tcp_tx_control_workspace_bytes(n: int) -> int:
+    """``aipstack_tcp_tx_control_workspace_bytes``: the workspace :func:`tcp_tx_control` needs for
+    n descriptors."""
+    return int(_lib.load().aipstack_tcp_tx_control_workspace_bytes(max(n, 0)))
+
+
+class TcpControlSegments:
+    """What :func:`tcp_tx_control` leaves (device tensors, n descriptors): ``headers`` (uint8, n
+    slots of ``hdr_stride`` bytes; slot i holds descriptor i's segment), ``hdr_lens`` (int32: 54,
+    58, 62 or 0), ``chunk_index`` (int64, n + 1, all zero: no chunks), ``status`` (uint8:
+    AIPSTACK_TCP_CTL_*) and ``counts`` (int64, 2: emitted, invalid). ``chunk_addr`` /
+    ``chunk_len`` are empty, which makes the object a ``segments`` argument of
+    :func:`tx_linearise` / :func:`tx_linearise_slotted` (an invalid descriptor is skipped);
+    ``headers``, ``hdr_stride`` and ``hdr_lens`` are what :func:`tx_resolve` takes."""
+
+    def __init__(self, headers, hdr_stride, hdr_lens, chunk_index, status, counts):
+        torch = _torch()
+        self.headers, self.hdr_stride, self.hdr_lens = headers, hdr_stride, hdr_lens
+        self.chunk_index, self.status, self.counts = chunk_index, status, counts
+        self.chunk_addr = torch.empty(0, dtype=torch.int64, device=headers.device)
+        self.chunk_len = torch.empty(0, dtype=torch.int32, device=headers.device)
+
+    @property
+    def n(self) -> int:
+        return self.chunk_index.numel() - 1
+
+
+def tcp_tx_control(ctl, iface, *, tcp_ttl: int = 64, hdr_stride: int = 64, headers=None,
+                   workspace=None, stream=None) -> TcpControlSegments:
+    """TCP segments without data on the GPU (``aipstack_tcp_tx_control``): the batched form of the
+    reference's ``send_tcp_nodata`` for SYN, SYN-ACK, empty ACK, FIN and RST. ``ctl``: the
+    descriptors, a ``TCP_CTL_DTYPE`` host array (:func:`tcp_ctl`; uploaded on the launch stream)
+    or a device uint8 tensor of whole 32-byte descriptors already resident. ``iface``: an
+    ``ICMP_IFACE_DTYPE`` record (:func:`icmp_iface`; its ``mac`` is the Ethernet source, its
+    ``ip_id`` the Ident of the first valid descriptor; ``tcp_ttl`` is the TTL). The j-th valid
+    descriptor carries the Ident ``ip_id + j`` and lies in slot i of the header ring ``headers``
+    (a uint8 device tensor of n slots of ``hdr_stride`` >= 62 bytes; fresh and zeroed when None);
+    bytes 0..5 of a slot are 0 until :func:`tx_resolve` writes the next hop's MAC. Returns a
+    :class:`TcpControlSegments`; the host advances its Ident counter by ``counts[0]`` (chksum.h
+    has the rules and the byte layout). With no descriptor at all nothing runs: ``chunk_index``
+    (one entry) and ``counts`` are set to 0."""
+    torch = _torch()
+    f = np.ascontiguousarray(iface, dtype=ICMP_IFACE_DTYPE).reshape(-1)
+    if f.size != 1:
+        raise ValueError("iface must be one ICMP_IFACE_DTYPE record")
+    if hasattr(ctl, "data_ptr"):
+        dev = ctl.device
+    elif headers is not None:
+        dev = headers.device
+    else:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    launch_stream = _launch_stream(stream, dev)
+    with torch.cuda.stream(launch_stream):  # an upload is ordered before the call
+        if not hasattr(ctl, "data_ptr"):
+            k = np.ascontiguousarray(ctl, dtype=TCP_CTL_DTYPE).reshape(-1)
+            given, ctl = None, torch.from_numpy(k.view(np.uint8).copy()).to(dev)
+        else:
+            given = ctl
+        _require_device(ctl, "ctl")
+        nbytes = ctl.numel() * ctl.element_size()
+        if nbytes % 32:
+            raise ValueError("ctl must hold whole 32-byte descriptors")
+        n = nbytes // 32
+        if headers is None:
+            headers = torch.zeros(max(n, 1) * hdr_stride, dtype=torch.uint8, device=dev)
+        _require_device(headers, "headers")
+        _same_device(ctl, headers, "ctl and headers")
+        if headers.element_size() != 1 or hdr_stride <= 0 or headers.numel() < n * hdr_stride:
+            raise ValueError("headers must be a uint8 device tensor of n whole slots of hdr_stride bytes")
+        res = TcpControlSegments(headers, hdr_stride,
+                                 torch.empty(n, dtype=torch.int32, device=dev),
+                                 torch.empty(n + 1, dtype=torch.int64, device=dev),
+                                 torch.empty(n, dtype=torch.uint8, device=dev),
+                                 torch.empty(2, dtype=torch.int64, device=dev))
+        if n == 0:  # nothing to launch
+            res.chunk_index.zero_()
+            res.counts.zero_()
+            return res
+    workspace, ws_bytes = _workspace(workspace, tcp_tx_control_workspace_bytes(n), headers, "headers")
+    _check(_lib.load().aipstack_tcp_tx_control(
+        ctl.data_ptr(), n, f.ctypes.data, tcp_ttl, headers.data_ptr(), hdr_stride,
+        res.hdr_lens.data_ptr(), res.chunk_index.data_ptr(), res.status.data_ptr(),
+        res.counts.data_ptr(), workspace.data_ptr(), ws_bytes, _stream_handle(launch_stream)),
+        "aipstack_tcp_tx_control")
+    workspace.record_stream(launch_stream)
+    if ctl is not given:
+        ctl.record_stream(launch_stream)
+    return res
+
+
 class SplitFrames:
     """What :func:`split_frames` returns (host arrays): ``headers`` (n slots of ``hdr_stride``
     bytes), ``hdr_lens`` (uint32), ``payload`` (uint8, every chunk's bytes) and ``chunks``

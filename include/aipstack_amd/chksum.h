@@ -1732,6 +1732,69 @@ int aipstack_chksum_abi_version(void);
  * lets a test or a deployment tell a library from a stale build. */
 const char *aipstack_chksum_source_digest(void);
 
+/* ---- TCP segments without data: SYN, SYN-ACK, ACK, FIN, RST ------------------------- */
+
+/* The batched form of the reference's send_tcp_nodata (tcp/IpTcpProto_output.h:1337-1404) under
+ * sendIp4Dgram (ip/IpStack.h:423-453), for its five callers: pcb_send_syn (the SYN and the
+ * SYN-ACK, :79-122), pcb_send_empty_ack (:126-134), pcb_output_empty_fin_segment (:1149-1175)
+ * and pcb_send_rst / send_rst (:137-142, :1012-1018). The host's state machine decides what to
+ * send and fills one descriptor per segment; the call builds the header slot, both checksums
+ * included, for aipstack_tx_resolve and aipstack_tx_linearise, as the RSTs of
+ * aipstack_tcp_rx_respond are.
+ *
+ * A descriptor is invalid (AIPSTACK_TCP_CTL_INVALID) only if reserved0 or reserved1 is nonzero
+ * or options has a bit besides AIPSTACK_TCP_OPT_MSS | AIPSTACK_TCP_OPT_WND_SCALE: its slot stays
+ * untouched, d_hdr_len[i] = 0 and it takes no Ident. Flags and option subsets are not
+ * restricted (send_tcp_nodata does not restrict them).
+ *
+ * The j-th valid descriptor in descriptor order, with olen = 4 * popcount(options) and
+ * H = 54 + olen: Ethernet destination 0 (aipstack_tx_resolve writes it), source h_iface->mac,
+ * EtherType 0x0800; IPv4 0x4500, total length 40 + olen, Ident h_iface->ip_id + j mod 2^16,
+ * flags/offset 0x4000 (DF), TTL tcp_ttl, protocol 6, source local_addr, destination remote_addr,
+ * the header checksum; TCP ports, seq, ack, OffsetFlags (5 + olen/4) << 12 | flags, window, the
+ * checksum over the pseudo-header (length 20 + olen), the header and the options, stored as
+ * computed (0 stays 0x0000), urgent 0; then the options as WriteTcpOptions writes them
+ * (tcp/TcpOptions.h:141-157): 02 04 mss_hi mss_lo if _OPT_MSS, then 01 03 03 wnd_scale if
+ * _OPT_WND_SCALE.
+ *
+ * Outputs, all written for all n descriptors in every call, from the inputs alone: the H bytes
+ * at d_hdr + i*hdr_stride and zeros in [H, min(hdr_stride, 64)) of the slot (bytes past 64 and an
+ * invalid descriptor's whole slot stay untouched); d_hdr_len[i] = H or 0; d_chunk_index[0..n] = 0
+ * (no chunks); d_status[i] = AIPSTACK_TCP_CTL_EMITTED or _CTL_INVALID; d_counts[0] = emitted
+ * (the host advances its Ident counter by it), d_counts[1] = invalid. d_ctl, d_hdr, d_hdr_len,
+ * d_chunk_index, d_status, d_counts and d_workspace are DEVICE memory, h_iface HOST memory (read
+ * before the call returns; local_addr, bcast_addr, mtu, ttl and flags are validated as
+ * aipstack_icmp_rx_respond does, mac and ip_id are used). Three stream-ordered launches, no
+ * allocation, no synchronisation.
+ *
+ * Returns _EINVAL before any work for a null pointer, hdr_stride < AIPSTACK_TCP_CTL_MAX_HEADER,
+ * n > 2^40, tcp_ttl outside 1..255, an interface aipstack_icmp_rx_respond rejects, d_ctl,
+ * d_chunk_index, d_counts or d_workspace not 8-byte aligned, d_hdr_len not 4-byte aligned, or
+ * workspace_bytes < aipstack_tcp_tx_control_workspace_bytes(n). n == 0 is a no-op. */
+#define AIPSTACK_TCP_CTL_MAX_HEADER 62u  /* 54 + MSS 4 + window scale 4 */
+#define AIPSTACK_TCP_CTL_EMITTED  48     /* per descriptor: the slot holds its segment */
+#define AIPSTACK_TCP_CTL_INVALID  49     /* per descriptor: a reserved field or an unknown option bit */
+
+typedef struct aipstack_tcp_ctl {   /* 32 bytes, 8-byte aligned, host-made */
+    uint32_t local_addr, remote_addr;   /* TcpPcbKey, host order as in aipstack_tcp_pcb_key */
+    uint16_t local_port, remote_port;
+    uint32_t seq, ack;                  /* stored as given (ack also where ACK is clear) */
+    uint16_t window;                    /* stored as given (send_rst passes 0) */
+    uint16_t mss;                       /* the MSS option's value */
+    uint8_t  flags;                     /* low byte of OffsetFlags: FIN 01 SYN 02 RST 04 PSH 08 ACK 10 URG 20 ECE 40 CWR 80 */
+    uint8_t  options;                   /* AIPSTACK_TCP_OPT_MSS | AIPSTACK_TCP_OPT_WND_SCALE */
+    uint8_t  wnd_scale;
+    uint8_t  reserved0;                 /* 0 */
+    uint32_t reserved1;                 /* 0 */
+} aipstack_tcp_ctl;
+
+uint64_t aipstack_tcp_tx_control_workspace_bytes(uint64_t n);
+int aipstack_tcp_tx_control(const aipstack_tcp_ctl *d_ctl, uint64_t n,
+                            const aipstack_icmp_iface *h_iface, uint32_t tcp_ttl,
+                            void *d_hdr, uint64_t hdr_stride, uint32_t *d_hdr_len,
+                            uint64_t *d_chunk_index, uint8_t *d_status, uint64_t *d_counts,
+                            void *d_workspace, uint64_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
